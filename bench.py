@@ -15,9 +15,21 @@ sharded across ranks (strong scaling): every rank runs the (cheap, deterministic
 partial d(loss)/d(latent grid) and the IM-NET gradients are summed with RCCL all-reduces, and the UNet backward
 is replicated.
 
-Prints ONE JSON line (rank 0) with the contract fields plus ``roofline`` (dominant kernel, HIP-event timed) and
-``cpu_baseline`` (the CPU oracle = restatement of the reference path, timed on the host cores on a bounded
-sample).
+Prints ONE JSON line (rank 0) with the contract fields (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``,
+``ms_per_step`` = wall time of one timed step).  A plain run does only that: set up, warm up, time ``--steps`` steps, write
+the outputs (``--dump-outputs DIR``) and print the line.  ``--full`` adds everything else the line used to carry, each
+measured after the timed region: ``roofline`` (dominant kernel, HIP-event timed), per-rank and collective diagnostics,
+side figures, the fp32x3 second line, ``other_configs`` (child runs) and ``cpu_baseline`` (the CPU oracle = restatement
+of the reference path, timed on the host cores on a bounded sample).
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller -- the losses and the gradient of every
+parameter, summed over ranks (the launch-bound workloads: also the parameters after the optimizer step) -- as
+``DIR/<name>.npy`` in float32, at most 64 MB in all.  Inputs and initial weights are seeded and the step workloads (c2, c5)
+run in the library's deterministic mode (``reproducible_mode``), so the same arguments give the same outputs every run and
+two builds can be compared output for output; ``--nondeterministic`` times the library's default mode instead, and the line
+says which mode ran (``deterministic``).  The launch-bound workloads (train_default, c1) are not switched -- the
+deterministic mode nearly doubles their step time -- and their dumps agree between runs only to the drift of an optimizer
+loop fed with fp32-atomic gradients.  The child runs of ``other_configs`` keep the default mode of their earlier figures.
 """
 import argparse
 import json
@@ -103,6 +115,59 @@ def make_inputs(n_pts, dev, seed=0, igres=(32, 128, 128), n_out=4):
     return crop, pts, tgt
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6      # --dump-outputs: at most 64 MB in all, .npy headers included
+
+
+def step_outputs(losses, modules, with_params=False):
+    """What one step hands its caller: the losses, the gradient of every parameter (and, after an optimizer step, the
+    parameters themselves), keyed by file name."""
+    out = dict(zip(("loss", "reg_loss", "pde_loss"), losses))
+    for prefix, m in modules:
+        for name, p in m.named_parameters():
+            if p.grad is not None:
+                out["grad.%s.%s" % (prefix, name)] = p.grad
+            if with_params:
+                out["param.%s.%s" % (prefix, name)] = p
+    return out
+
+
+def reproducible_mode(args):
+    """Unless ``--nondeterministic`` is given, the benchmarked step runs in the library's deterministic mode:
+    every sum the step accumulates with atomics -- U-Net convolution weight / bias gradients, BatchNorm statistics and
+    backward sums, IM-NET weight gradients, the loss sums -- goes to order-independent long accumulators, so the same
+    arguments give bit-identical losses and gradients run after run.  In the default mode the U-Net's deepest BatchNorm
+    levels, which normalise over a handful of voxels, amplify the atomics' summation-order rounding into differences of
+    ~0.5 % of its gradient between runs.  Set in ``main`` and not at import: tests import this module for its constants.
+    Returns the mode the step runs in (``--nondeterministic`` leaves STPDE_DETERMINISTIC in charge)."""
+    from space_time_pde_amd import _lib
+    if not args.nondeterministic:
+        _lib.deterministic = True
+    return bool(_lib.deterministic)
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write {name: tensor} as DIR/<name>.npy: float64 tensors as float64, everything else as float32.  When the arrays
+    together exceed ``limit`` bytes, every array of more than 4096 elements is replaced by a fixed sample of its flattened
+    elements: the sorted first k of a permutation seeded by 0, k the same fraction of every array -- the indices depend
+    only on the array's size and the total, so two builds run with the same arguments write the same sample."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32)
+    total = sum(a.numel() * a.element_size() for a in host.values())
+    floors = sum(4096 * a.element_size() for a in host.values())     # (an array is never cut below 4096 elements)
+    frac = 1.0 if total <= limit else max(0.0, limit - floors) / total
+    for name, a in sorted(host.items()):
+        if frac < 1.0 and a.numel() > 4096:
+            g = torch.Generator().manual_seed(0)
+            k = max(4096, int(a.numel() * frac))
+            idx = torch.randperm(a.numel(), generator=g)[:k].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a.numpy())
+
+
 def c5_layer(pde_module):
     layer = pde_module.PDELayer(*C5_VARS)
     for name, eq in C5_EQS.items():
@@ -170,7 +235,8 @@ def other_configs(args):
     out = {}
     for name, extra in runs:
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", str(warm),
-               "--points", str(args.points), "--act", args.act, "--no-cpu-baseline", "--no-other-configs", "--sub"] + extra
+               "--points", str(args.points), "--act", args.act, "--full", "--nondeterministic", "--no-cpu-baseline", "--no-other-configs",
+               "--sub"] + extra
         rec = dict(cmd="python bench.py " + " ".join(cmd[2:]))
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
@@ -231,7 +297,7 @@ def small_workload(args):
     spec = SMALL_WORKLOADS[args.workload]
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    from space_time_pde_amd import implicit_net, lig_jet, local_implicit_grid as lig, nonlinearities, optim, physics, unet3d
+    from space_time_pde_amd import _lib, implicit_net, lig_jet, local_implicit_grid as lig, nonlinearities, optim, physics, unet3d
     from space_time_pde_amd.train_step import GraphedStep, sharded_step
     torch.manual_seed(1)
     B, N, igres = spec["batch"], spec["points"], spec["igres"]
@@ -272,11 +338,13 @@ def small_workload(args):
             if item:
                 v = loss.item()                                            # train.py:84 ``tot_loss += loss.item()``
         torch.cuda.synchronize()
+        last_loss[0] = loss
         return 1e3 * (time.perf_counter() - t0) / steps, float(loss)
 
+    last_loss = [None]
+    n0 = lig.stats["hip_jet_calls"]
     for _ in range(max(args.warmup, 3)):
         eager_step()
-    n0 = lig.stats["hip_jet_calls"]
     if args.profile_only:
         # child run of this workload: kernel dispatches and device time of ONE eager step through torch.profiler (roctracer).
         # In a process of its own: a profiler that is unavailable or crashes must not cost the parent its line.
@@ -293,12 +361,19 @@ def small_workload(args):
         print(json.dumps(rec))
         return rec
     import gc
-    gc.collect()
-    gc.disable()
-    ms_eager, loss_e = timed(eager_step, args.steps)
-    ms_eager_async, _ = timed(eager_step, args.steps, item=False)
-    gc.enable()
-    assert lig.stats["hip_jet_calls"] == n0 + 2 * args.steps, "HIP jet path was not taken"
+    # eager timings: the headline when the capture failed, diagnostics (--full) beside the graph's otherwise
+    ms_eager = ms_eager_async = loss_e = None
+    n_eager = max(args.warmup, 3)
+    if args.full or gstep is None:
+        gc.collect()
+        gc.disable()
+        ms_eager, loss_e = timed(eager_step, args.steps)
+        n_eager += args.steps
+        if args.full:
+            ms_eager_async, _ = timed(eager_step, args.steps, item=False)
+            n_eager += args.steps
+        gc.enable()
+    assert lig.stats["hip_jet_calls"] == n0 + n_eager, "HIP jet path was not taken"
     # the same iteration with forward + backward replayed from the HIP graph
     ms_graph = ms_graph_async = loss_g = None
     if gstep is not None:
@@ -309,48 +384,53 @@ def small_workload(args):
             opt.step()
             return loss
 
-        for _ in range(3):
+        for _ in range(max(args.warmup, 3)):                               # the graph path's own warm-up
             graph_step()
         gc.collect()
         gc.disable()
         ms_graph, loss_g = timed(graph_step, args.steps)
-        ms_graph_async, _ = timed(graph_step, args.steps, item=False)
+        if args.full:
+            ms_graph_async, _ = timed(graph_step, args.steps, item=False)
         gc.enable()
-    # dispatches and device time of ONE eager step: a child run of this script (see --profile-only above); the library's own
-    # dispatch trace (its kernels only, torch's elementwise / cat / copy launches not seen) if that fails
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs([last_loss[0]], [("unet", unet), ("imnet", net)], with_params=True))
+    # dispatches and device time of ONE eager step (--full): a child run of this script (see --profile-only above); the
+    # library's own dispatch trace (its kernels only, torch's elementwise / cat / copy launches not seen) if that fails
     disp = ksum = prof_err = None
-    try:
-        import subprocess
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--act", args.act, "--profile-only"]
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-        line = [l for l in r.stdout.splitlines() if l.startswith("{")]
-        if r.returncode == 0 and line:
-            j = json.loads(line[-1])
-            disp, ksum = j["dispatches_per_step"], j["kernel_ms_per_step"]
-        else:
-            prof_err = "child rc %d: %s" % (r.returncode, r.stderr[-300:])
-    except Exception as e:  # noqa: BLE001
-        prof_err = "%s: %s" % (type(e).__name__, e)
-    if disp is None:
-        from space_time_pde_amd import _lib
-        with _lib.dispatch_trace() as tr:
-            eager_step()
-        disp = float(len(tr.kernels))
+    if args.full:
+        try:
+            import subprocess
+            cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--act", args.act, "--profile-only"]
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            line = [l for l in r.stdout.splitlines() if l.startswith("{")]
+            if r.returncode == 0 and line:
+                j = json.loads(line[-1])
+                disp, ksum = j["dispatches_per_step"], j["kernel_ms_per_step"]
+            else:
+                prof_err = "child rc %d: %s" % (r.returncode, r.stderr[-300:])
+        except Exception as e:  # noqa: BLE001
+            prof_err = "%s: %s" % (type(e).__name__, e)
+        if disp is None:
+            with _lib.dispatch_trace() as tr:
+                eager_step()
+            disp = float(len(tr.kernels))
     ms = ms_graph if ms_graph is not None else ms_eager
     pts_step = B * N
     out = {
         "metric": "query-points/sec (whole training iteration: fwd + PDE-residual bwd + clip + Adam), rb2d",
         "value": pts_step / (ms * 1e-3), "unit": "query-points/s", "n_gpus": 1, "steps": args.steps, "warmup": max(args.warmup, 3),
         "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "deterministic": bool(_lib.deterministic),
         "launch_mode": "HIP graph replay (forward + backward captured once; optimizer launch + loss read-back per step)"
                        if ms_graph is not None else "eager",
-        "ms_per_step_eager": round(ms_eager, 3), "ms_per_step_eager_no_readback": round(ms_eager_async, 3),
+        "ms_per_step_eager": None if ms_eager is None else round(ms_eager, 3),
+        "ms_per_step_eager_no_readback": None if ms_eager_async is None else round(ms_eager_async, 3),
         "ms_per_step_graph": None if ms_graph is None else round(ms_graph, 3),
         "ms_per_step_graph_no_readback": None if ms_graph_async is None else round(ms_graph_async, 3),
         "graph_error": graph_err,
         "dispatches_per_step": disp, "kernel_ms_per_step": None if ksum is None else round(ksum, 3),
         "step_over_kernel_time": None if not ksum else round(ms / ksum, 2),
-        "step_over_kernel_time_eager": None if not ksum else round(ms_eager / ksum, 2),
+        "step_over_kernel_time_eager": None if not ksum or ms_eager is None else round(ms_eager / ksum, 2),
         "profiler_error": prof_err,
         "config": {"workload": spec["name"] + ", RB2 (3 transport + continuity), ImNet nf=32 %s, L1 losses, alpha_pde=0.0125, "
                    "FusedClipAdam(lr=1e-2, clip_grad=1)" % args.act, "points": pts_step, "batch": B,
@@ -359,7 +439,7 @@ def small_workload(args):
                      "traffic": None,
                      "note": "a %d-point step is ~%d dispatches of microseconds each: no kernel of this workload is near a "
                              "hardware roof; the figure of merit is step time over the sum of kernel time (below 1 when the "
-                             "graph's side-stream branches overlap)" % (pts_step, int(disp))},
+                             "graph's side-stream branches overlap)" % (pts_step, int(disp))} if args.full else None,
     }
     print(json.dumps(out))
     return out
@@ -403,6 +483,16 @@ def main(argv=None):
     ap.add_argument("--mem-budget-gb", type=float, default=None,
                     help="device-memory budget of the jet call's stash + scratch (lig_jet.set_memory_budget): above it the "
                          "backward recomputes the forward chunk by chunk; the line reports peak_GB either way")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the diagnostics: roofline / per-kernel times, per-rank and "
+                         "collective figures, side figures, the fp32x3 line, other_configs, cpu_baseline (off: the plain "
+                         "run times the steps and prints the contract fields only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, parameter gradients) as DIR/<name>.npy")
+    ap.add_argument("--nondeterministic", action="store_true",
+                    help="time the library's default mode (fp32 atomics) instead of its deterministic mode; the outputs of "
+                         "two runs then agree only to amplified summation-order rounding.  The launch-bound workloads "
+                         "(train_default, c1) are never switched to the deterministic mode")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the `other_configs` block (BASELINE configs[3] and configs[4], each timed by a child run of this "
@@ -418,6 +508,7 @@ def main(argv=None):
         args.traffic_json = os.path.join(ROOT, "profiles", "pmc_traffic_c4_bf16.json")
     if args.workload in SMALL_WORKLOADS:
         return small_workload(args)
+    det = reproducible_mode(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_spawn(args.gpus, list(sys.argv[1:] if argv is None else argv))
 
@@ -487,8 +578,7 @@ def main(argv=None):
     def step():
         for p in params + uparams:
             p.grad = None
-        loss, _, _ = sharded_step(unet, net, layer, crop, pts, tgt, args.points, ALPHA_REG, ALPHA_PDE, "l1")
-        return loss
+        return sharded_step(unet, net, layer, crop, pts, tgt, args.points, ALPHA_REG, ALPHA_PDE, "l1")
 
     def sync():
         torch.cuda.synchronize()
@@ -508,11 +598,12 @@ def main(argv=None):
     t0 = time.perf_counter()
     for k in range(args.steps):
         sev[k][0].record()
-        loss = step()
+        last = step()
         sev[k][1].record()
     sync()
     dt = time.perf_counter() - t0
     gc.enable()
+    loss = last[0]
     from space_time_pde_amd import train_step as _ts
     coll_rec = list(_ts.last_collectives)        # (what, bytes) of the collectives of the last timed step
     step_ms_seq = [a.elapsed_time(b) for a, b in sev]
@@ -520,150 +611,158 @@ def main(argv=None):
     step_ms_median = step_ms[len(step_ms) // 2]
     peak_gb = torch.cuda.max_memory_allocated(dev) / 2 ** 30      # warm-up + timed steps (allocated, not reserved)
     recompute_steps = lig_jet.stats["recompute_steps"]
-    # Per-rank diagnosis of a multi-GPU line (outside the timed region, VERDICT r3 #3c): what THIS rank's step costs with no
-    # collective in it (same shard, same kernels) and what
-    # its replicated U-Net costs alone; rank 0 prints the per-rank lists and ms_per_step - max(compute_ms) as the exposed
-    # communication (+ load imbalance) of the timed steps.
-    def local_step():
-        for p in params + uparams:
-            p.grad = None
-        sharded_step(unet, net, layer, crop, pts, tgt, args.points, ALPHA_REG, ALPHA_PDE, "l1", distributed=False)
-
-    local_step()
-    ce = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    torch.cuda.synchronize()
-    ce[0].record()
-    for _ in range(2):
-        local_step()
-    ce[1].record()
-    torch.cuda.synchronize()
-    compute_ms = ce[0].elapsed_time(ce[1]) / 2
-    gcot = torch.randn(1, *igres, 32, device=dev).permute(0, 4, 1, 2, 3)
-    ue = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    uf, ub = [], []
-    for it in range(3):
-        for p in uparams:
-            p.grad = None
-        ue[0].record()
-        y = unet(crop)
-        ue[1].record()
-        y.backward(gcot)
-        ue[2].record()
-        torch.cuda.synchronize()
-        if it:
-            uf.append(ue[0].elapsed_time(ue[1]))
-            ub.append(ue[1].elapsed_time(ue[2]))
-    del y, gcot
-    per_rank = torch.tensor([compute_ms, sum(uf) / len(uf), sum(ub) / len(ub), peak_gb], device=dev, dtype=torch.float64)
-    if world > 1:
-        allr = [torch.zeros_like(per_rank) for _ in range(world)]
-        dist.all_gather(allr, per_rank)
-        per_rank = torch.stack(allr)
-    else:
-        per_rank = per_rank[None]
-    per_rank = per_rank.cpu().tolist()
-    # the collectives of one step (what, bytes) as the step itself recorded them, and what each costs ALONE on this process
-    # group (median of 5 all-reduces of the same size, outside the timed region): with per_rank.compute_ms this separates
-    # bandwidth / latency of the exchange from load imbalance in a multi-GPU line
-    coll = [dict(what=w, bytes=int(b)) for w, b in coll_rec]
-    if dist.is_initialized():
-        for c in coll:
-            buf = torch.zeros(max(1, c["bytes"] // 4), device=dev)
-            dist.all_reduce(buf)
-            torch.cuda.synchronize()
-            ts = []
-            for _ in range(5):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                dist.all_reduce(buf)
-                e1.record()
-                torch.cuda.synchronize()
-                ts.append(e0.elapsed_time(e1))
-            c["alone_ms"] = round(sorted(ts)[2], 3)
-            del buf
-    # per-kernel HIP-event timings: a SECOND pass outside the timed region (the event pairs around ~70 launches per
-    # step would otherwise sit inside it)
-    lig_jet.profile = {}
-    # (2 until round 5, 4 in round 5: one 120 ms outlier among four launches decided which kernel was "dominant", VERDICT r5
-    # weak #3; since round 6 eight steps, and dominance is decided on the MEDIAN launch time)
-    nprof = 8
-    unet.register_forward_pre_hook(lambda m, i: pending.append(torch.cuda.Event(enable_timing=True)) or pending[-1].record())
-    unet.register_forward_hook(_post)
-    for _ in range(nprof):
-        step()
-    sync()
-    prof = lig_jet.profile
-    lig_jet.profile = None
-    tt = torch.tensor([dt], device=dev, dtype=torch.float64)
+    # ms_per_step and peak_GB of a multi-GPU line: the slowest rank
+    tt = torch.tensor([dt, peak_gb], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-    dt = tt.item()
+    dt, peak_gb_all = tt.tolist()
     assert lig.stats["hip_jet_calls"] >= args.steps + args.warmup, "HIP jet path was not taken"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(last, [("unet", unet), ("imnet", net)]))
+    coll = [dict(what=w, bytes=int(b)) for w, b in coll_rec]
 
-    # SURVEY 8(d) side figures (outside the timed region, rank 0 of a single-GPU run only): value-only inference rate,
-    # the step without the UNet, and the gather stage against its algorithmic 1036 B / point
-    side = None
-    if rank == 0 and world == 1 and not args.sub:
-        import torch.nn.functional as F
-        with torch.no_grad():
-            latent = unet(crop).permute(0, 2, 3, 4, 1)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        with torch.no_grad():
-            lig.query_local_implicit_grid(net, latent, pts, 0., 1.)
-            ev[0].record()
-            for _ in range(3):
-                lig.query_local_implicit_grid(net, latent, pts, 0., 1.)
-            ev[1].record()
-
-        def lig_only_step():
-            for p in params:
+    # --full: the diagnostics below, each measured after the timed region
+    per_rank = side = x3 = roofline = None
+    if args.full:
+        # Per-rank diagnosis of a multi-GPU line (outside the timed region, VERDICT r3 #3c): what THIS rank's step costs with no
+        # collective in it (same shard, same kernels) and what
+        # its replicated U-Net costs alone; rank 0 prints the per-rank lists and ms_per_step - max(compute_ms) as the exposed
+        # communication (+ load imbalance) of the timed steps.
+        def local_step():
+            for p in params + uparams:
                 p.grad = None
-            lat = latent.detach().requires_grad_(True)
-            layer.update_forward_method(lambda q: lig.query_local_implicit_grid(net, lat, q, 0., 1.))
-            pred, res = layer(pts, return_residue=True)
-            st = torch.stack(list(res.values()), 0)
-            (ALPHA_REG * F.l1_loss(pred, tgt) + ALPHA_PDE * st.abs().mean()).backward()
+            sharded_step(unet, net, layer, crop, pts, tgt, args.points, ALPHA_REG, ALPHA_PDE, "l1", distributed=False)
 
-        lig_only_step()
-        ev[2].record()
-        for _ in range(2):
-            lig_only_step()
-        ev[3].record()
+        local_step()
+        ce = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         torch.cuda.synchronize()
-        side = dict(inference_value_only_points_per_s=round(3 * args.points / (ev[0].elapsed_time(ev[1]) * 1e-3)),
-                    lig_only_step_points_per_s=round(2 * args.points / (ev[2].elapsed_time(ev[3]) * 1e-3)))
-    # Second headline-grade line: the SAME step with the wide layers' products as exact-split bf16 MFMAs
-    # ("fp32x3": every fp32-tolerance parity test is parametrised over it, tests/test_gpu_reference_fixtures.py), timed over the
-    # same --steps with the same bracket as `value`, then two profiled steps for its own dominant-kernel roofline.  `value` /
-    # `dtype` above stay the exact-fp32 MFMA path.
-    x3 = None
-    if rank == 0 and world == 1 and args.mlp_precision == "fp32" and not c5 and not args.sub and not args.no_other_configs:
-        if side is not None:
-            del latent
-        lig_jet.set_mlp_precision("fp32x3")
-        try:
-            for _ in range(max(1, min(args.warmup, 2))):
-                step()
-            sync()
-            gc.collect()
-            gc.disable()
-            t3 = time.perf_counter()
-            for _ in range(args.steps):
-                l3 = step()
-            sync()
-            dt3 = time.perf_counter() - t3
-            gc.enable()
-            lig_jet.profile = {}
-            for _ in range(nprof):
-                step()
-            sync()
-            x3 = dict(dt=dt3, loss=float(l3), prof=lig_jet.profile)
-            lig_jet.profile = None
-        finally:
-            lig_jet.set_mlp_precision("fp32")
-            lig_jet.profile = None
+        ce[0].record()
+        for _ in range(2):
+            local_step()
+        ce[1].record()
+        torch.cuda.synchronize()
+        compute_ms = ce[0].elapsed_time(ce[1]) / 2
+        gcot = torch.randn(1, *igres, 32, device=dev).permute(0, 4, 1, 2, 3)
+        ue = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        uf, ub = [], []
+        for it in range(3):
+            for p in uparams:
+                p.grad = None
+            ue[0].record()
+            y = unet(crop)
+            ue[1].record()
+            y.backward(gcot)
+            ue[2].record()
+            torch.cuda.synchronize()
+            if it:
+                uf.append(ue[0].elapsed_time(ue[1]))
+                ub.append(ue[1].elapsed_time(ue[2]))
+        del y, gcot
+        per_rank = torch.tensor([compute_ms, sum(uf) / len(uf), sum(ub) / len(ub), peak_gb], device=dev, dtype=torch.float64)
+        if world > 1:
+            allr = [torch.zeros_like(per_rank) for _ in range(world)]
+            dist.all_gather(allr, per_rank)
+            per_rank = torch.stack(allr)
+        else:
+            per_rank = per_rank[None]
+        per_rank = per_rank.cpu().tolist()
+        # the collectives of one step (what, bytes) as the step itself recorded them, and what each costs ALONE on this process
+        # group (median of 5 all-reduces of the same size, outside the timed region): with per_rank.compute_ms this separates
+        # bandwidth / latency of the exchange from load imbalance in a multi-GPU line
+        if dist.is_initialized():
+            for c in coll:
+                buf = torch.zeros(max(1, c["bytes"] // 4), device=dev)
+                dist.all_reduce(buf)
+                torch.cuda.synchronize()
+                ts = []
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    dist.all_reduce(buf)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ts.append(e0.elapsed_time(e1))
+                c["alone_ms"] = round(sorted(ts)[2], 3)
+                del buf
+        # per-kernel HIP-event timings: a SECOND pass outside the timed region (the event pairs around ~70 launches per
+        # step would otherwise sit inside it)
+        lig_jet.profile = {}
+        # (2 until round 5, 4 in round 5: one 120 ms outlier among four launches decided which kernel was "dominant", VERDICT r5
+        # weak #3; since round 6 eight steps, and dominance is decided on the MEDIAN launch time)
+        nprof = 8
+        unet.register_forward_pre_hook(lambda m, i: pending.append(torch.cuda.Event(enable_timing=True)) or pending[-1].record())
+        unet.register_forward_hook(_post)
+        for _ in range(nprof):
+            step()
+        sync()
+        prof = lig_jet.profile
+        lig_jet.profile = None
 
-    if rank == 0:
+        # SURVEY 8(d) side figures (outside the timed region, rank 0 of a single-GPU run only): value-only inference rate,
+        # the step without the UNet, and the gather stage against its algorithmic 1036 B / point
+        side = None
+        if rank == 0 and world == 1 and not args.sub:
+            import torch.nn.functional as F
+            with torch.no_grad():
+                latent = unet(crop).permute(0, 2, 3, 4, 1)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            with torch.no_grad():
+                lig.query_local_implicit_grid(net, latent, pts, 0., 1.)
+                ev[0].record()
+                for _ in range(3):
+                    lig.query_local_implicit_grid(net, latent, pts, 0., 1.)
+                ev[1].record()
+
+            def lig_only_step():
+                for p in params:
+                    p.grad = None
+                lat = latent.detach().requires_grad_(True)
+                layer.update_forward_method(lambda q: lig.query_local_implicit_grid(net, lat, q, 0., 1.))
+                pred, res = layer(pts, return_residue=True)
+                st = torch.stack(list(res.values()), 0)
+                (ALPHA_REG * F.l1_loss(pred, tgt) + ALPHA_PDE * st.abs().mean()).backward()
+
+            lig_only_step()
+            ev[2].record()
+            for _ in range(2):
+                lig_only_step()
+            ev[3].record()
+            torch.cuda.synchronize()
+            side = dict(inference_value_only_points_per_s=round(3 * args.points / (ev[0].elapsed_time(ev[1]) * 1e-3)),
+                        lig_only_step_points_per_s=round(2 * args.points / (ev[2].elapsed_time(ev[3]) * 1e-3)))
+        # Second headline-grade line: the SAME step with the wide layers' products as exact-split bf16 MFMAs
+        # ("fp32x3": every fp32-tolerance parity test is parametrised over it, tests/test_gpu_reference_fixtures.py), timed over the
+        # same --steps with the same bracket as `value`, then two profiled steps for its own dominant-kernel roofline.  `value` /
+        # `dtype` above stay the exact-fp32 MFMA path.
+        x3 = None
+        if rank == 0 and world == 1 and args.mlp_precision == "fp32" and not c5 and not args.sub and not args.no_other_configs:
+            if side is not None:
+                del latent
+            lig_jet.set_mlp_precision("fp32x3")
+            try:
+                for _ in range(max(1, min(args.warmup, 2))):
+                    step()
+                sync()
+                gc.collect()
+                gc.disable()
+                t3 = time.perf_counter()
+                for _ in range(args.steps):
+                    l3 = step()[0]
+                sync()
+                dt3 = time.perf_counter() - t3
+                gc.enable()
+                lig_jet.profile = {}
+                for _ in range(nprof):
+                    step()
+                sync()
+                x3 = dict(dt=dt3, loss=float(l3), prof=lig_jet.profile)
+                lig_jet.profile = None
+            finally:
+                lig_jet.set_mlp_precision("fp32")
+                lig_jet.profile = None
+
+    bf16 = args.mlp_precision == "bf16"
+    if rank == 0 and args.full:
         smooth = args.act not in ("relu", "leakyrelu")
         # piecewise-linear activations have identically zero second-order MLP jets.  c5: the equation set needs
         # 4 second-order jets (xx, yy, xy, tt); SURVEY: "replace 32*4 by 32*5 in M and T"
@@ -748,7 +847,6 @@ def main(argv=None):
             roofline["gather_stage"] = gs
         if side:
             roofline["side_figures"] = side
-        bf16 = args.mlp_precision == "bf16"
         if bf16:
             # bf16 operands: the layer kernels are priced against BOTH roofs -- HBM on the bytes of the packed layer buffers
             # (what the kernel has to move) and the dense bf16 MFMA peak on the executed products -- and the line carries the
@@ -791,6 +889,7 @@ def main(argv=None):
             roofline.pop("executed_tflops", None)
             roofline.pop("executed_frac", None)
             roofline["step_frac_note"] = "step_frac_per_gpu is the algorithmic fp32 FLOP rate of the step over the fp32-MFMA peak (157.3): a speed-up figure in this mode, not a utilisation"
+    if rank == 0:
         out = {
             "metric": ("query-points/sec (fwd+PDE-residual bwd), user-string 5-channel equations, 128^3 latent" if c5 else
                        "query-points/sec (fwd+PDE-residual bwd), rb2d 128^3 latent"),
@@ -805,17 +904,9 @@ def main(argv=None):
             "ms_per_step_hip_event_median": round(step_ms_median, 3),
             "ms_per_step_hip_event_min_max": [round(step_ms[0], 3), round(step_ms[-1], 3)],
             "ms_per_step_hip_event_sequence": [round(v, 2) for v in step_ms_seq],
-            "peak_GB": round(max(r[3] for r in per_rank), 2),
+            "peak_GB": round(peak_gb_all, 2),
             "recompute_steps": recompute_steps,
             "collectives_per_step": coll,
-            "per_rank": {"compute_ms": [round(r[0], 2) for r in per_rank],
-                         "unet_fwd_ms": [round(r[1], 2) for r in per_rank], "unet_bwd_ms": [round(r[2], 2) for r in per_rank],
-                         "peak_GB": [round(r[3], 2) for r in per_rank],
-                         "exposed_comm_ms": round(1e3 * dt / args.steps - max(r[0] for r in per_rank), 2),
-                         "note": "compute_ms = this rank's step on its shard with no collective in it (2 steps after the timed "
-                                 "region); unet_*_ms = its replicated U-Net alone, eager launches with their gaps (inside the "
-                                 "step the backward runs after the IM-NET backward on the same stream); exposed_comm_ms = "
-                                 "ms_per_step - max(compute_ms): exchange + load imbalance not hidden behind compute"},
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -825,6 +916,7 @@ def main(argv=None):
                       "the bf16 MFMA pipe; everything else exact f32)"
                       if args.mlp_precision == "fp32x3" else "f32"),
             "data": "synthetic",
+            "deterministic": det,
             "config": {"workload": ("BASELINE configs[4]: latent [1,%d,%d,%d,32], 2^%d query points, 5-output user-string "
                                     "equations %s (3 inputs x, y, t; second derivatives xx, yy, xy, tt -> the (3,%d) stream set), "
                                     "ImNet nf=32 out_features=5 %s, L1 losses, backward to ImNet + UNet3d parameters"
@@ -836,8 +928,18 @@ def main(argv=None):
                        "points": args.points, "parallelism": "points sharded x%d" % world,
                        "unet": "UNet3d(igres=%s, nf=16, mf=256) fwd+bwd inside the timed step" % (igres,),
                        "loss": float(loss)},
-            "roofline": roofline,
         }
+        if args.full:
+            out["per_rank"] = {
+                "compute_ms": [round(r[0], 2) for r in per_rank],
+                "unet_fwd_ms": [round(r[1], 2) for r in per_rank], "unet_bwd_ms": [round(r[2], 2) for r in per_rank],
+                "peak_GB": [round(r[3], 2) for r in per_rank],
+                "exposed_comm_ms": round(1e3 * dt / args.steps - max(r[0] for r in per_rank), 2),
+                "note": "compute_ms = this rank's step on its shard with no collective in it (2 steps after the timed "
+                        "region); unet_*_ms = its replicated U-Net alone, eager launches with their gaps (inside the "
+                        "step the backward runs after the IM-NET backward on the same stream); exposed_comm_ms = "
+                        "ms_per_step - max(compute_ms): exchange + load imbalance not hidden behind compute"}
+            out["roofline"] = roofline
         if x3 is not None:
             # fp32x3: the wide layers issue SIX bf16 MFMA products per fp32 product, so the pipe that bounds its kernels is the
             # bf16 one: its dominant kernel's executed bf16 work (combined-stream jet) against the dense bf16 peak
@@ -870,9 +972,9 @@ def main(argv=None):
                      "rate it stands for over the exact-fp32 MFMA peak (157.3): a speed-up figure, may exceed 1; timed over "
                      "the same --steps as `value`, HIP-event kernel times from %d extra steps" % nprof,
                 kernels={k: round(v["total_ms"] / nprof, 2) for k, v in sorted(k3.items())})
-        if world == 1 and not args.sub and not args.no_other_configs and not c5 and args.mlp_precision == "fp32":
+        if args.full and world == 1 and not args.sub and not args.no_other_configs and not c5 and args.mlp_precision == "fp32":
             out["other_configs"] = other_configs(args)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.act)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

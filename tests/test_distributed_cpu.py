@@ -4,11 +4,21 @@ import os
 import socket
 import sys
 
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture
+def restore_num_threads():
+    """Put the intra-op thread count back after a test that compares with its workers at one thread: later tests in the
+    same process run with the host's count (test_reference_fixtures.py's C1 U-Net step rounds differently on one thread)."""
+    prev = torch.get_num_threads()
+    yield
+    torch.set_num_threads(prev)
 
 
 def _build(seed=0):
@@ -45,7 +55,7 @@ def _worker(rank, world, port, out):
     dist.destroy_process_group()
 
 
-def test_two_rank_step_equals_single_process(tmp_path):
+def test_two_rank_step_equals_single_process(tmp_path, restore_num_threads):
     sys.path.insert(0, ROOT)
     from space_time_pde_amd.train_step import sharded_step
     s = socket.socket()
@@ -84,7 +94,7 @@ def _worker_dp(rank, world, port, out):
     dist.destroy_process_group()
 
 
-def test_two_rank_data_parallel_step_averages_gradients(tmp_path):
+def test_two_rank_data_parallel_step_averages_gradients(tmp_path, restore_num_threads):
     """The reference's batch-of-crops split (train_ddp.py:401-406): gradients = mean over ranks of the local ones."""
     sys.path.insert(0, ROOT)
     from space_time_pde_amd.train_step import data_parallel_step

@@ -30,16 +30,16 @@ rocprofv3 --kernel-trace --stats -d /tmp/ktd -- python $R/bench.py --workload tr
 python $R/tools/rocprof_summary.py trace $(find /tmp/ktd -name "*.db" | head -1) > $P/r6_train_default_kernel_trace_stats.txt
 cd $R
 python tools/make_traffic_json.py $P/r6_pmc_FETCH_SIZE.txt $P/r6_pmc_WRITE_SIZE.txt 1048576 softplus $P/pmc_traffic.json
-python bench.py --traffic-json $P/pmc_traffic.json > $O/r6_bench.json 2> $O/r6_bench.err
-python bench.py --act leakyrelu --no-cpu-baseline --no-other-configs > $O/r6_bench_leakyrelu.json 2> /dev/null
-python bench.py --mlp-precision fp32x3 --no-cpu-baseline > $O/r6_bench_fp32x3.json 2> /dev/null
-python bench.py --mlp-precision bf16 --no-cpu-baseline > $O/r6_bench_bf16_mode_c2grid.json 2> /dev/null
-python bench.py --mlp-precision bf16 --igres 64 256 256 --no-cpu-baseline > $O/r6_bench_config4_bf16.json 2> /dev/null
-for p in 524288 262144 131072; do python bench.py --points $p --steps 8 --warmup 2 --no-cpu-baseline --no-other-configs > $O/r6_proxy_$p.json 2> /dev/null; done
-STPDE_BENCH_ONE_DEVICE=1 STPDE_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 4 --warmup 2 --no-cpu-baseline > $O/r6_bench_2rank_gloo.json 2> /dev/null
-python bench.py --workload c5 --steps 5 --warmup 2 --no-cpu-baseline > $O/r6_bench_c5.json 2> /dev/null
-python bench.py --workload train_default --steps 100 > $O/r6_bench_train_default.json 2> /dev/null
-python bench.py --workload c1 --steps 100 > $O/r6_bench_config0_gpu.json 2> /dev/null
+python bench.py --full --nondeterministic --traffic-json $P/pmc_traffic.json > $O/r6_bench.json 2> $O/r6_bench.err
+python bench.py --full --nondeterministic --act leakyrelu --no-cpu-baseline --no-other-configs > $O/r6_bench_leakyrelu.json 2> /dev/null
+python bench.py --full --nondeterministic --mlp-precision fp32x3 --no-cpu-baseline > $O/r6_bench_fp32x3.json 2> /dev/null
+python bench.py --full --nondeterministic --mlp-precision bf16 --no-cpu-baseline > $O/r6_bench_bf16_mode_c2grid.json 2> /dev/null
+python bench.py --full --nondeterministic --mlp-precision bf16 --igres 64 256 256 --no-cpu-baseline > $O/r6_bench_config4_bf16.json 2> /dev/null
+for p in 524288 262144 131072; do python bench.py --full --nondeterministic --points $p --steps 8 --warmup 2 --no-cpu-baseline --no-other-configs > $O/r6_proxy_$p.json 2> /dev/null; done
+STPDE_BENCH_ONE_DEVICE=1 STPDE_BENCH_BACKEND=gloo python bench.py --full --nondeterministic --gpus 2 --steps 4 --warmup 2 --no-cpu-baseline > $O/r6_bench_2rank_gloo.json 2> /dev/null
+python bench.py --full --nondeterministic --workload c5 --steps 5 --warmup 2 --no-cpu-baseline > $O/r6_bench_c5.json 2> /dev/null
+python bench.py --full --nondeterministic --workload train_default --steps 100 > $O/r6_bench_train_default.json 2> /dev/null
+python bench.py --full --nondeterministic --workload c1 --steps 100 > $O/r6_bench_config0_gpu.json 2> /dev/null
 python tools/bench_inference.py > $O/r6_inference.json 2> /dev/null
 python tools/bench_next_rows.py > $O/r6_next_rows.json 2> /dev/null
 python tools/det_cost.py > $O/r6_det_cost.json 2> /dev/null

@@ -403,6 +403,17 @@ typedef struct {
    * stpde_det_finalize turns an accumulator array into fp32 (statistics / backward sums are read by the BatchNorm kernels
    * directly: a single replica [2][C][6] in the same scratch).  The forward does not split its taps over workgroups. */
   int det;
+  /* Operand mode of the 3x3x3 GEMM products (0 = fp32 operands on v_mfma_f32_16x16x4_f32, today's path).  1 = bf16 operands:
+   * every product of the call takes both operands rounded to bf16 (round-to-nearest-even, v_cvt_pk_bf16_f32, NaN stays NaN)
+   * and accumulates in fp32 on v_mfma_f32_16x16x16_bf16 (one instruction per four fp32 k-steps, same tiles, same order):
+   *   forward         y  = bias + sum_tap bf16(W_tap) . bf16(x_tap)   (bias, statistics epilogue, tap-split atomics in fp32)
+   *   input gradient  dx = sum bf16(W^T) . bf16(gy)                   (the EPI 2 mask / BatchNorm-backward sums from the fp32
+   *                                                                    result)
+   *   weight grad.    dW = sum_vox bf16(ybar) x bf16(x_shifted)       (fp32 or deterministic long accumulators);
+   *                   dbias stays the fp32 sum of the UNROUNDED ybar
+   * Activations, packs and outputs stay fp32; 1x1x1 convolutions (HBM-bound) have no bf16 mode: mfma_bf16 = 1 with ksize 1 is
+   * refused (STPDE_E_BADARG), as is any value other than 0 / 1 (3 is reserved for an exact-split fp32x3 mode). */
+  int mfma_bf16;
 } stpde_conv3d_desc;
 /* acc [n][STPDE_DET_K] long accumulators (a deterministic-mode destination, see stpde_conv3d_desc.det) -> out [n] fp32. */
 #define STPDE_DET_K 6

@@ -19,7 +19,7 @@ _SOURCES = ["jet_layer.hip", "jet_layer_s00.hip", "jet_layer_s03.hip", "jet_laye
 _HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics",
              "--offload-compress"]
 
-ABI_VERSION = 314   # == stpde_version() of the library these ctypes signatures were written for (csrc/api.cpp)
+ABI_VERSION = 315   # == stpde_version() of the library these ctypes signatures were written for (csrc/api.cpp)
 
 ACT_CODES = {"tanh": 0, "relu": 1, "softplus": 2, "elu": 3, "swish": 4, "leakyrelu": 5}
 PBAR_SLOTS = 64   # STPDE_PBAR_SLOTS: accumulation slots of the swish-beta adjoint
@@ -68,7 +68,7 @@ LOSS_DET = 16      # STPDE_LOSS_DET: stpde_loss_sum into a long accumulator
 
 class Conv3dDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("T", C.c_int), ("Z", C.c_int), ("X", C.c_int), ("Ci", C.c_int), ("Co", C.c_int),
-                ("ksize", C.c_int), ("det", C.c_int)]
+                ("ksize", C.c_int), ("det", C.c_int), ("mfma_bf16", C.c_int)]
 
 
 class Conv3dFusedArgs(C.Structure):     # stpde_conv3d_fused_args

@@ -14,7 +14,10 @@
 // SPLIT (small volumes = the deep U-Net levels, where a handful of waves would otherwise walk 27 taps x all channel
 // tiles serially): blockIdx.z owns a slice of the taps and adds its partial sums to the zero-filled output with fp32
 // atomics; taps whose 16 neighbours all fall outside the volume are skipped.
-template <int MC, int VT, bool SPLIT = false>
+// BF (3x3x3 only, stpde_conv3d_desc.mfma_bf16 = 1): both operands rounded to bf16, the four fp32 k-steps of a (tap, k-tile)
+// become ONE v_mfma_f32_16x16x16_bf16 -- its lane l holds k = 4 (l >> 4) + e in element e, the channel the fp32 path feeds
+// in k-step e, so the float4 fragments are the operands as they are; accumulation, bias and atomics stay fp32.
+template <int MC, int VT, bool SPLIT = false, bool BF = false>
 __global__ __launch_bounds__(256) void k_conv3d_fwd(ConvArgs a) {
   const int lane = threadIdx.x & 63;
   const int tile0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * VT;
@@ -64,14 +67,32 @@ __global__ __launch_bounds__(256) void k_conv3d_fwd(ConvArgs a) {
           if (nb[t] < 0) B[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
         const float* wp = a.w + ((size_t)(tap * KT + kt) * MT + mt0) * 256 + lo;
+        if constexpr (BF) {
+          // all MC weight fragments requested before the first conversion (converted one by one behind their own load, the
+          // requests went out one at a time, each waited for: the tap-split kernel of the deep levels ran 1.7x slower than fp32)
+          f32x4 w[MC];
 #pragma unroll
-        for (int mi = 0; mi < MC; ++mi) {
-          const int mic = mt0 + mi < MT ? mi : 0;
-          f32x4 w = ld4(wp + (size_t)mic * 256);
+          for (int mi = 0; mi < MC; ++mi) w[mi] = ld4(wp + (size_t)(mt0 + mi < MT ? mi : 0) * 256);
+          __builtin_amdgcn_sched_barrier(0);
+          bf16x4 Bb[VT];
 #pragma unroll
-          for (int r = 0; r < 4; ++r)
+          for (int t = 0; t < VT; ++t) Bb[t] = cvt_bf4(B[t]);
 #pragma unroll
-            for (int t = 0; t < VT; ++t) acc[t][mi] = mfma4(w[r], B[t][r], acc[t][mi]);
+          for (int mi = 0; mi < MC; ++mi) {
+            const bf16x4 wb = cvt_bf4(w[mi]);
+#pragma unroll
+            for (int t = 0; t < VT; ++t) acc[t][mi] = mfma_bf16k(wb, Bb[t], acc[t][mi]);
+          }
+        } else {
+#pragma unroll
+          for (int mi = 0; mi < MC; ++mi) {
+            const int mic = mt0 + mi < MT ? mi : 0;
+            f32x4 w = ld4(wp + (size_t)mic * 256);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+              for (int t = 0; t < VT; ++t) acc[t][mi] = mfma4(w[r], B[t][r], acc[t][mi]);
+          }
         }
       }
     }
@@ -103,8 +124,12 @@ __global__ __launch_bounds__(256) void k_conv3d_fwd(ConvArgs a) {
 // fp32 atomics per block, so at most gridDim.x atomics hit any dW address.
 // ONLOAD (round 4, 1x1x1): x is the raw output of the previous convolution of a residual block and the convolution consumed
 // max(0, bn(x)) applied on load (k_conv_fused); the same per-channel transform on the operand dwords here.
-template <int MCW, int KCW, int TG, bool ONLOAD = false>
+// BF (3x3x3, mfma_bf16 = 1): the 4 k-steps of a voxel tile (lane 16k+i: voxel 4s+k) become one v_mfma_f32_16x16x16_bf16 on the
+// rounded fragments (element s of lane 16k+i = k-step s: both operands use the same voxel map); the bias gradient is summed
+// from the unrounded ybar fragments.
+template <int MCW, int KCW, int TG, bool ONLOAD = false, bool BF = false>
 __global__ __launch_bounds__(256) void k_conv3d_wgrad(ConvArgs a) {
+  static_assert(!(BF && ONLOAD), "bf16 operands: 3x3x3 weight gradients only");
   __shared__ float red[4][256];
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
@@ -199,14 +224,28 @@ __global__ __launch_bounds__(256) void k_conv3d_wgrad(ConvArgs a) {
   for (int tile = blockIdx.x * 4 + wv; tile < ntiles; tile += gridDim.x * 4) {
     Frag cur;
     load(tile, cur);
+    if constexpr (BF) {
+      bf16x4 pb[MCW];
 #pragma unroll
-    for (int s = 0; s < 4; ++s)
+      for (int mi = 0; mi < MCW; ++mi) pb[mi] = cvt_bf4(f32x4{cur.pa[0][mi], cur.pa[1][mi], cur.pa[2][mi], cur.pa[3][mi]});
 #pragma unroll
       for (int tg = 0; tg < TG; ++tg)
 #pragma unroll
-        for (int mi = 0; mi < MCW; ++mi)
+        for (int ki = 0; ki < KCW; ++ki) {
+          const bf16x4 qb = cvt_bf4(f32x4{cur.qb[0][tg][ki], cur.qb[1][tg][ki], cur.qb[2][tg][ki], cur.qb[3][tg][ki]});
 #pragma unroll
-          for (int ki = 0; ki < KCW; ++ki) acc[tg][mi][ki] = mfma4(cur.pa[s][mi], cur.qb[s][tg][ki], acc[tg][mi][ki]);
+          for (int mi = 0; mi < MCW; ++mi) acc[tg][mi][ki] = mfma_bf16k(pb[mi], qb, acc[tg][mi][ki]);
+        }
+    } else {
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int tg = 0; tg < TG; ++tg)
+#pragma unroll
+          for (int mi = 0; mi < MCW; ++mi)
+#pragma unroll
+            for (int ki = 0; ki < KCW; ++ki) acc[tg][mi][ki] = mfma4(cur.pa[s][mi], cur.qb[s][tg][ki], acc[tg][mi][ki]);
+    }
     if (dob) {
 #pragma unroll
       for (int mi = 0; mi < MCW; ++mi) bs[mi] += (cur.pa[0][mi] + cur.pa[1][mi]) + (cur.pa[2][mi] + cur.pa[3][mi]);
@@ -258,7 +297,9 @@ __global__ __launch_bounds__(256) void k_conv3d_wgrad(ConvArgs a) {
 // row base and validity are wave-uniform, a lane's offset in the row, its LDS address and its swizzle do not depend on the
 // block and are computed once; out-of-volume requests hit the descriptor's range check and return zeros.  The fragment reads
 // of the MFMA loop use per-tap lane addresses computed once per launch + one add per (t, z) row of the block + immediates.
-template <int CIT, int COT, int TX = 32, int COS = COT>
+// BF (mfma_bf16 = 1): the 4 k-steps of a 16-voxel tile and tap are read first and contracted by ONE v_mfma_f32_16x16x16_bf16
+// on the rounded fragments (element sk = k-step sk for both operands); the bias gradient comes from the unrounded ybar in LDS.
+template <int CIT, int COT, int TX = 32, int COS = COT, bool BF = false>
 __global__ __launch_bounds__(512) void k_conv3d_wgrad_lds(ConvArgs a) {
   constexpr int TT = 2, TZ = 4, HT = TT + 2, HZ = TZ + 2, HX = TX + 2, NXH = TX / 16;
   constexpr int CoF = 16 * COS;                        // channels of a voxel of ybar in memory
@@ -396,18 +437,40 @@ __global__ __launch_bounds__(512) void k_conv3d_wgrad_lds(ConvArgs a) {
         for (int co = 0; co < COT; ++co)
 #pragma unroll
           for (int sk = 0; sk < 4; ++sk) pa[co][sk] = ayr[co & 1][(16 * xh + 4 * sk) * Co + 16 * (co & ~1)];
+        if constexpr (BF) {
+          bf16x4 pb[COT];
 #pragma unroll
-        for (int ti = 0; ti < 4; ++ti) {
-          if (ti < ntap_w) {                           // wave-uniform
+          for (int co = 0; co < COT; ++co) pb[co] = cvt_bf4(f32x4{pa[co][0], pa[co][1], pa[co][2], pa[co][3]});
 #pragma unroll
-            for (int sk = 0; sk < 4; ++sk) {
-              float qb[CIT];
+          for (int ti = 0; ti < 4; ++ti) {
+            if (ti < ntap_w) {                         // wave-uniform
+              float qf[CIT][4];
 #pragma unroll
-              for (int ci = 0; ci < CIT; ++ci) qb[ci] = axr[ti][ci & 1][(16 * xh + 4 * sk) * Ci + 16 * (ci & ~1)];
+              for (int sk = 0; sk < 4; ++sk)
 #pragma unroll
-              for (int co = 0; co < COT; ++co)
+                for (int ci = 0; ci < CIT; ++ci) qf[ci][sk] = axr[ti][ci & 1][(16 * xh + 4 * sk) * Ci + 16 * (ci & ~1)];
 #pragma unroll
-                for (int ci = 0; ci < CIT; ++ci) acc[ti][co][ci] = mfma4(pa[co][sk], qb[ci], acc[ti][co][ci]);
+              for (int ci = 0; ci < CIT; ++ci) {
+                const bf16x4 qb = cvt_bf4(f32x4{qf[ci][0], qf[ci][1], qf[ci][2], qf[ci][3]});
+#pragma unroll
+                for (int co = 0; co < COT; ++co) acc[ti][co][ci] = mfma_bf16k(pb[co], qb, acc[ti][co][ci]);
+              }
+            }
+          }
+        } else {
+#pragma unroll
+          for (int ti = 0; ti < 4; ++ti) {
+            if (ti < ntap_w) {                         // wave-uniform
+#pragma unroll
+              for (int sk = 0; sk < 4; ++sk) {
+                float qb[CIT];
+#pragma unroll
+                for (int ci = 0; ci < CIT; ++ci) qb[ci] = axr[ti][ci & 1][(16 * xh + 4 * sk) * Ci + 16 * (ci & ~1)];
+#pragma unroll
+                for (int co = 0; co < COT; ++co)
+#pragma unroll
+                  for (int ci = 0; ci < CIT; ++ci) acc[ti][co][ci] = mfma4(pa[co][sk], qb[ci], acc[ti][co][ci]);
+              }
             }
           }
         }
@@ -601,7 +664,7 @@ static int check_conv(const stpde_conv3d_desc* d) {
     stpde_set_error("conv3d: volume too large for int32 voxel indices");
     return STPDE_E_BADARG;
   }
-  return STPDE_OK;
+  return stpde_check_conv_mode(d, "conv3d");
 }
 
 extern "C" int stpde_conv3d_fwd(const stpde_conv3d_desc* d, const float* x, const float* w_pack, const float* bias,
@@ -624,9 +687,18 @@ extern "C" int stpde_conv3d_fwd(const stpde_conv3d_desc* d, const float* x, cons
   const int MT = d->Co / 16;
   const hipStream_t st = (hipStream_t)stream;
   // MC = output-channel tiles per pass: never more than the layer has (a clamped tile would redo real MFMA work)
+  // bf16 operands (mfma_bf16 = 1, ksize 3 only: check_conv): the same instantiations with BF set, launched under the same rules
+  const bool bf = d->mfma_bf16 == 1;
   if (ntiles >= 16384) {   // big volumes: 4 voxel tiles per wave (4x weight reuse), one wave walks all chunks
     const dim3 grid((ntiles + 15) / 16, 1);
-    if (MT == 1)
+    if (bf) {
+      if (MT == 1)
+        STPDE_LAUNCH((k_conv3d_fwd<1, 4, false, true>), grid, dim3(256), 0, st, a);
+      else if (MT == 2)
+        STPDE_LAUNCH((k_conv3d_fwd<2, 4, false, true>), grid, dim3(256), 0, st, a);
+      else
+        STPDE_LAUNCH((k_conv3d_fwd<4, 4, false, true>), grid, dim3(256), 0, st, a);
+    } else if (MT == 1)
       STPDE_LAUNCH((k_conv3d_fwd<1, 4>), grid, dim3(256), 0, st, a);
     else if (MT == 2)
       STPDE_LAUNCH((k_conv3d_fwd<2, 4>), grid, dim3(256), 0, st, a);
@@ -643,7 +715,17 @@ extern "C" int stpde_conv3d_fwd(const stpde_conv3d_desc* d, const float* x, cons
     }
     if (gz > 1) {
       (void)hipMemsetAsync(y, 0, (size_t)a.nvox * d->Co * sizeof(float), st);
-      STPDE_LAUNCH((k_conv3d_fwd<4, 1, true>), dim3(gx, gy, gz), dim3(256), 0, st, a);
+      if (bf)
+        STPDE_LAUNCH((k_conv3d_fwd<4, 1, true, true>), dim3(gx, gy, gz), dim3(256), 0, st, a);
+      else
+        STPDE_LAUNCH((k_conv3d_fwd<4, 1, true>), dim3(gx, gy, gz), dim3(256), 0, st, a);
+    } else if (bf) {
+      if (MT == 1)
+        STPDE_LAUNCH((k_conv3d_fwd<1, 1, false, true>), dim3(gx, gy), dim3(256), 0, st, a);
+      else if (MT == 2)
+        STPDE_LAUNCH((k_conv3d_fwd<2, 1, false, true>), dim3(gx, gy), dim3(256), 0, st, a);
+      else
+        STPDE_LAUNCH((k_conv3d_fwd<4, 1, false, true>), dim3(gx, gy), dim3(256), 0, st, a);
     } else if (MT == 1) {
       STPDE_LAUNCH((k_conv3d_fwd<1, 1>), dim3(gx, gy), dim3(256), 0, st, a);
     } else if (MT == 2) {
@@ -713,6 +795,7 @@ static int conv3d_wgrad(const stpde_conv3d_desc* d, const float* x, const float*
   if (launch_conv1_wgrad_lds<false>(a, (hipStream_t)stream)) return stpde_check_launch("k_conv1_wgrad_lds");
   const int ntiles = (a.nvox + 15) / 16;
   const int KT = d->Ci / 16, MT = d->Co / 16;
+  const bool bf = d->mfma_bf16 == 1;       // bf16 operands: ksize 3 only (check_conv)
   // (tap group, co block, ci block) triples on blockIdx.y; voxel-tile stripes on blockIdx.x: ~2048 blocks in total
   // (8 waves per SIMD hide the dword-load latency), at most 1024 stripes (= atomic adds any dW element receives)
   auto stripes = [&](int gy) {
@@ -740,7 +823,16 @@ static int conv3d_wgrad(const stpde_conv3d_desc* d, const float* x, const float*
     else if (nblk < half_below)
       gx = 128;
     if (gx > nblk) gx = nblk;
-    if (KT == 1 && MT == 1)
+    if (bf) {
+      if (KT == 1 && MT == 1)
+        STPDE_LAUNCH((k_conv3d_wgrad_lds<1, 1, 32, 1, true>), dim3(gx), dim3(512), 0, (hipStream_t)stream, a);
+      else if (KT == 2 && MT == 2)
+        STPDE_LAUNCH((k_conv3d_wgrad_lds<2, 2, 32, 2, true>), dim3(gx), dim3(512), 0, (hipStream_t)stream, a);
+      else if (KT == 1)
+        STPDE_LAUNCH((k_conv3d_wgrad_lds<1, 2, 32, 2, true>), dim3(gx), dim3(512), 0, (hipStream_t)stream, a);
+      else
+        STPDE_LAUNCH((k_conv3d_wgrad_lds<2, 1, 32, 1, true>), dim3(gx), dim3(512), 0, (hipStream_t)stream, a);
+    } else if (KT == 1 && MT == 1)
       STPDE_LAUNCH((k_conv3d_wgrad_lds<1, 1>), dim3(gx), dim3(512), 0, (hipStream_t)stream, a);
     else if (KT == 2 && MT == 2)
       STPDE_LAUNCH((k_conv3d_wgrad_lds<2, 2>), dim3(gx), dim3(512), 0, (hipStream_t)stream, a);
@@ -757,14 +849,23 @@ static int conv3d_wgrad(const stpde_conv3d_desc* d, const float* x, const float*
       nblk16 >= 256) {
     int gx = 64;                             // x 4 output tiles: one workgroup (116 KB of LDS) per CU
     if (gx > nblk16) gx = nblk16;
-    STPDE_LAUNCH((k_conv3d_wgrad_lds<4, 1, 16, 4>), dim3(gx, 4), dim3(512), 0, (hipStream_t)stream, a);
+    if (bf)
+      STPDE_LAUNCH((k_conv3d_wgrad_lds<4, 1, 16, 4, true>), dim3(gx, 4), dim3(512), 0, (hipStream_t)stream, a);
+    else
+      STPDE_LAUNCH((k_conv3d_wgrad_lds<4, 1, 16, 4>), dim3(gx, 4), dim3(512), 0, (hipStream_t)stream, a);
     return stpde_check_launch("k_conv3d_wgrad_lds");
   }
   if (d->ksize == 3 && KT == 1 && MT == 1) {
-    STPDE_LAUNCH((k_conv3d_wgrad<1, 1, 9>), dim3(stripes(3), 3), dim3(256), 0, (hipStream_t)stream, a);
+    if (bf)
+      STPDE_LAUNCH((k_conv3d_wgrad<1, 1, 9, false, true>), dim3(stripes(3), 3), dim3(256), 0, (hipStream_t)stream, a);
+    else
+      STPDE_LAUNCH((k_conv3d_wgrad<1, 1, 9>), dim3(stripes(3), 3), dim3(256), 0, (hipStream_t)stream, a);
   } else if (d->ksize == 3) {
     const int gy = 9 * ((MT + 1) / 2) * ((KT + 1) / 2);
-    STPDE_LAUNCH((k_conv3d_wgrad<2, 2, 3>), dim3(stripes(gy), gy), dim3(256), 0, (hipStream_t)stream, a);
+    if (bf)
+      STPDE_LAUNCH((k_conv3d_wgrad<2, 2, 3, false, true>), dim3(stripes(gy), gy), dim3(256), 0, (hipStream_t)stream, a);
+    else
+      STPDE_LAUNCH((k_conv3d_wgrad<2, 2, 3>), dim3(stripes(gy), gy), dim3(256), 0, (hipStream_t)stream, a);
   } else {
     const int gy = ((MT + 1) / 2) * ((KT + 1) / 2);
     STPDE_LAUNCH((k_conv3d_wgrad<2, 2, 1>), dim3(stripes(gy), gy), dim3(256), 0, (hipStream_t)stream, a);

@@ -26,9 +26,12 @@ struct FusedArgs {
 };
 
 // MC output tiles per pass, VT voxel tiles per wave, K3: 3x3x3 (else 1x1x1)
-template <int MC, int VT, bool K3, int DUAL, bool ONLOAD, int EPI>
+// BF (3x3x3, mfma_bf16 = 1): bf16 operands, one v_mfma_f32_16x16x16_bf16 per (tap, k-tile) as in k_conv3d_fwd; the epilogues
+// work on the fp32 accumulators exactly as in the fp32 mode
+template <int MC, int VT, bool K3, int DUAL, bool ONLOAD, int EPI, bool BF = false>
 __global__ __launch_bounds__(256) void k_conv_fused(FusedArgs a) {
   static_assert(!(K3 && (DUAL || ONLOAD)), "dual / on-load variants are 1x1x1 only");
+  static_assert(!BF || K3, "bf16 operands: 3x3x3 only");
   __shared__ float tab[ONLOAD ? 3 * 512 : 1];           // mean, rstd * gamma, beta of the input channels
   __shared__ double red[EPI ? 4 * MC * 16 * 2 : 1];     // per-wave channel sums of the pass
   const stpde_conv3d_desc& d = a.f.d;
@@ -124,13 +127,30 @@ __global__ __launch_bounds__(256) void k_conv_fused(FusedArgs a) {
             }
             if (nb[t] < 0) B[t] = f32x4{0.f, 0.f, 0.f, 0.f};
           }
+          if constexpr (BF) {
+            // all weight fragments requested before the first conversion (as in k_conv3d_fwd)
+            f32x4 w[MC];
 #pragma unroll
-          for (int mi = 0; mi < MC; ++mi) {
-            const f32x4 w = ld4(wbase[mi] + (size_t)(tap * KT + kt) * wstride[mi]);
+            for (int mi = 0; mi < MC; ++mi) w[mi] = ld4(wbase[mi] + (size_t)(tap * KT + kt) * wstride[mi]);
+            __builtin_amdgcn_sched_barrier(0);
+            bf16x4 Bb[VT];
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
+            for (int t = 0; t < VT; ++t) Bb[t] = cvt_bf4(B[t]);
 #pragma unroll
-              for (int t = 0; t < VT; ++t) acc[t][mi] = mfma4(w[r], B[t][r], acc[t][mi]);
+            for (int mi = 0; mi < MC; ++mi) {
+              const bf16x4 wb = cvt_bf4(w[mi]);
+#pragma unroll
+              for (int t = 0; t < VT; ++t) acc[t][mi] = mfma_bf16k(wb, Bb[t], acc[t][mi]);
+            }
+          } else {
+#pragma unroll
+            for (int mi = 0; mi < MC; ++mi) {
+              const f32x4 w = ld4(wbase[mi] + (size_t)(tap * KT + kt) * wstride[mi]);
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int t = 0; t < VT; ++t) acc[t][mi] = mfma4(w[r], B[t][r], acc[t][mi]);
+            }
           }
         }
       }
@@ -269,8 +289,11 @@ __global__ __launch_bounds__(256) void k_conv_fused(FusedArgs a) {
 // Same MFMA order per output element as k_conv_fused (tap, k-tile, k-step): results are bit-identical.
 // EPI 1 / 2 (statistics, mask + BatchNorm-backward sums): per block as above, but the per-wave sums stay in fp64 registers
 // across the blocks of the launch and meet in LDS once at the end: one set of atomics per workgroup and launch.
+// BF (mfma_bf16 = 1): the fragments are rounded to bf16 in registers right before the MFMAs (the LDS tile stays fp32) and each
+// step's four k-steps are one v_mfma_f32_16x16x16_bf16 -- same instruction, same (tap, k-tile) order as k_conv_fused<.., BF>:
+// the two bf16 kernels stay bit-identical as well.
 // ------------------------------------------------------------------------------------------------------------------------
-template <int KT, int EPI>
+template <int KT, int EPI, bool BF = false>
 __global__ __launch_bounds__(256, 2) void k_conv3_lds(FusedArgs a) {
   constexpr int TT = 2, TZ = KT == 1 ? 4 : 2, TX = KT == 4 ? 16 : 32;
   constexpr int HZ = TZ + 2, HX = TX + 2, NH = (TT + 2) * HZ * HX, NV = TT * TZ * TX, NXH = TX / 16;
@@ -451,10 +474,16 @@ __global__ __launch_bounds__(256, 2) void k_conv3_lds(FusedArgs a) {
           else
             wnn = ld4(wrown + (size_t)(sI + 2 - NS) * (KT * 256));
           __builtin_amdgcn_sched_barrier(0);             // (else the scheduler sinks the requests below the MFMAs to reuse
-#pragma unroll                                           //  the registers of the current fragments: no prefetch at all)
-          for (int rr = 0; rr < 4; ++rr)
+          if constexpr (BF) {                            //  the registers of the current fragments: no prefetch at all)
+            const bf16x4 wb = cvt_bf4(wc);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = mfma4(wc[rr], Bc[t][rr], acc[t]);
+            for (int t = 0; t < 4; ++t) acc[t] = mfma_bf16k(wb, cvt_bf4(Bc[t]), acc[t]);
+          } else {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr)
+#pragma unroll
+              for (int t = 0; t < 4; ++t) acc[t] = mfma4(wc[rr], Bc[t][rr], acc[t]);
+          }
 #pragma unroll
           for (int t = 0; t < 4; ++t) Bc[t] = Bn[t];
           wc = wn;
@@ -559,11 +588,17 @@ static bool launch_conv3_lds(const FusedArgs& a0, hipStream_t st) {
   int gx = gx_env > 0 ? gx_env : 512;                    // two persistent workgroups (64 - 77 KB of LDS) per CU
   if (gx > nblk) gx = nblk;
   const FusedArgs& a = a0;
+  const bool bf = d.mfma_bf16 == 1;
 #define STPDE_C3L(K)                                                                  \
-  if (KT == K) {                                                                     \
+  if (KT == K && !bf) {                                                              \
     if constexpr (EPI == 0) STPDE_LAUNCH((k_conv3_lds<K, 0>), dim3(gx), dim3(256), 0, st, a); \
     if constexpr (EPI == 1) STPDE_LAUNCH((k_conv3_lds<K, 1>), dim3(gx), dim3(256), 0, st, a); \
     if constexpr (EPI == 2) STPDE_LAUNCH((k_conv3_lds<K, 2>), dim3(gx), dim3(256), 0, st, a); \
+  }                                                                                  \
+  if (KT == K && bf) {                                                               \
+    if constexpr (EPI == 0) STPDE_LAUNCH((k_conv3_lds<K, 0, true>), dim3(gx), dim3(256), 0, st, a); \
+    if constexpr (EPI == 1) STPDE_LAUNCH((k_conv3_lds<K, 1, true>), dim3(gx), dim3(256), 0, st, a); \
+    if constexpr (EPI == 2) STPDE_LAUNCH((k_conv3_lds<K, 2, true>), dim3(gx), dim3(256), 0, st, a); \
   }
   STPDE_C3L(1) STPDE_C3L(2) STPDE_C3L(4)
 #undef STPDE_C3L
@@ -572,6 +607,26 @@ static bool launch_conv3_lds(const FusedArgs& a0, hipStream_t st) {
 
 template <bool K3, int DUAL, bool ONLOAD, int EPI>
 static void launch_fused(const FusedArgs& a, int MT, bool big, dim3 grid, hipStream_t st) {
+  if constexpr (K3) {
+    if (a.f.d.mfma_bf16 == 1) {          // bf16 operands (3x3x3 only)
+      if (big) {
+        if (MT == 1)
+          STPDE_LAUNCH((k_conv_fused<1, 4, K3, DUAL, ONLOAD, EPI, true>), grid, dim3(256), 0, st, a);
+        else if (MT == 2)
+          STPDE_LAUNCH((k_conv_fused<2, 4, K3, DUAL, ONLOAD, EPI, true>), grid, dim3(256), 0, st, a);
+        else
+          STPDE_LAUNCH((k_conv_fused<4, 4, K3, DUAL, ONLOAD, EPI, true>), grid, dim3(256), 0, st, a);
+      } else {
+        if (MT == 1)
+          STPDE_LAUNCH((k_conv_fused<1, 1, K3, DUAL, ONLOAD, EPI, true>), grid, dim3(256), 0, st, a);
+        else if (MT == 2)
+          STPDE_LAUNCH((k_conv_fused<2, 1, K3, DUAL, ONLOAD, EPI, true>), grid, dim3(256), 0, st, a);
+        else
+          STPDE_LAUNCH((k_conv_fused<4, 1, K3, DUAL, ONLOAD, EPI, true>), grid, dim3(256), 0, st, a);
+      }
+      return;
+    }
+  }
   if (big) {
     if (MT == 1)
       STPDE_LAUNCH((k_conv_fused<1, 4, K3, DUAL, ONLOAD, EPI>), grid, dim3(256), 0, st, a);
@@ -602,6 +657,7 @@ extern "C" int stpde_conv3d_fused(const stpde_conv3d_fused_args* f, int* epilogu
   }
   const bool dual_out = f->y2 != nullptr, dual_in = f->x2 != nullptr, onload = f->in_sums != nullptr;
   const bool stats = f->out_sums != nullptr, mask = f->m != nullptr;
+  if (stpde_check_conv_mode(d, "conv3d_fused")) return STPDE_E_BADARG;
   if (!f->x || !f->w_pack || !f->y || (dual_out && (!f->wo2_pack || f->Co2 < 16 || (f->Co2 & 15))) ||
       (dual_in && (!f->w2_pack || f->Ci2 < 16 || (f->Ci2 & 15))) || (onload && (!f->in_stat || d->Ci > 512)) ||
       (mask && (!f->m_stat || !f->m_bsum)) || (d->ksize == 3 && (dual_out || dual_in || onload)) ||

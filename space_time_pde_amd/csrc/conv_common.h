@@ -70,3 +70,20 @@ __device__ __forceinline__ void tap_uniform(const stpde_conv3d_desc& d, int tap,
 __device__ __forceinline__ int tap_nb(const VoxN& v, unsigned mask, int off) {
   return (v.ok & mask) == mask ? v.lin + off : -1;
 }
+
+// stpde_conv3d_desc.mfma_bf16: 0 (fp32 operands) or 1 (bf16 operands, 3x3x3 only); anything else is refused with the reason
+static inline int stpde_check_conv_mode(const stpde_conv3d_desc* d, const char* who) {
+  if (d->mfma_bf16 != 0 && d->mfma_bf16 != 1) {
+    stpde_set_error("%s: mfma_bf16 = %d (0 = fp32 operands, 1 = bf16 operands; no other mode)", who, d->mfma_bf16);
+    return STPDE_E_BADARG;
+  }
+  if (d->mfma_bf16 == 1 && d->ksize != 3) {
+    stpde_set_error("%s: mfma_bf16 = 1 with ksize %d (bf16 operands are for 3x3x3 convolutions only)", who, d->ksize);
+    return STPDE_E_BADARG;
+  }
+  return STPDE_OK;
+}
+
+// fp32 -> bf16 operand fragment for the bf16-operand convolutions: two v_cvt_pk_bf16_f32 (round-to-nearest-even, a NaN stays a
+// NaN) -- the element-wise casts of to_bf4 compile to four single-input conversions and two v_perm_b32
+__device__ __forceinline__ bf16x4 cvt_bf4(f32x4 v) { return __builtin_convertvector(v, bf16x4); }

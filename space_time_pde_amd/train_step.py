@@ -234,7 +234,8 @@ class GraphedStep:
     Everything the step launches goes to torch's current stream, which is the capturing stream during capture: the library's
     kernels are launched through ``hipLaunchKernelGGL`` on that stream and are captured like torch's own.  The library never
     allocates device memory or synchronises (include/stpde_hip.h), so nothing in it is illegal under capture; host-side
-    decisions of the step (memory plan, kernel variants) depend on shapes only and are frozen at capture.
+    decisions of the step (memory plan, kernel variants) depend on shapes only and are frozen at capture.  So is the operand
+    precision of the U-Net's 3x3x3 convolutions (``unet3d.conv_precision``): a graph keeps the mode it was captured with.
 
     Inputs are copied into static buffers before each replay; ``.grad`` of every parameter is a static tensor of the graph's
     memory pool, rewritten by each replay (the optimizer step runs outside the graph, on those tensors).  Not for a

@@ -9,6 +9,14 @@ contiguous view that feeds the local-implicit-grid kernels directly.  BatchNorm 
 fused HIP kernels ``stpde_bn_fwd`` / ``stpde_bn_bwd``, max pooling and nearest up-sampling in ``stpde_resample3d``;
 only the channel concatenation of the skip connections is a torch copy.
 ``Encoder3d`` of the reference (src/unet3d.py:243-344) is dead code there and is not provided.
+
+Operand precision of the 3x3x3 convolutions: ``conv_precision`` (``STPDE_UNET_PRECISION``, default "fp32"; switch with
+``set_conv_precision``).  "bf16" rounds both operands of every GEMM product of the HIP 3x3x3 convolutions -- forward, input
+gradient, weight gradient -- to bf16 and accumulates in fp32 (``stpde_conv3d_desc.mfma_bf16``, include/stpde_hip.h); the
+1x1x1 convolutions, BatchNorm, pooling / up-sampling, the activations in memory, the weights and the bias gradients stay
+fp32.  The mode is read once per autograd node at forward time, so its backward uses the mode its forward ran in.
+``torch.autocast`` is not consulted, and convolutions outside the HIP envelope (``_hip_conv_ok``: torch's convolution)
+stay fp32 whatever the mode.
 """
 import ctypes as C
 import math
@@ -83,11 +91,32 @@ def _acc_value(acc, n):
     return out
 
 
-def _desc(x, ci, co, k):
+# Operand precision of the 3x3x3 convolutions (see the module docstring): "fp32" (exact fp32 MFMA, the default) or "bf16".
+conv_precision = os.getenv("STPDE_UNET_PRECISION", "fp32")
+
+
+def set_conv_precision(precision):
+    """Select "fp32" or "bf16" operands for the 3x3x3 convolutions of subsequent forward passes; returns the previous setting."""
+    global conv_precision
+    if precision not in ("fp32", "bf16"):
+        raise ValueError("U-Net conv precision must be 'fp32' or 'bf16' (got %r)" % (precision,))
+    prev, conv_precision = conv_precision, precision
+    return prev
+
+
+def _bf16():
+    """stpde_conv3d_desc.mfma_bf16 of a 3x3x3 convolution under the current mode (read once per node, at forward time)"""
+    if conv_precision not in ("fp32", "bf16"):
+        raise ValueError("STPDE_UNET_PRECISION / conv_precision must be 'fp32' or 'bf16' (got %r)" % (conv_precision,))
+    return 1 if conv_precision == "bf16" else 0
+
+
+def _desc(x, ci, co, k, bf=0):
     d = _lib.Conv3dDesc()
     d.B, d.T, d.Z, d.X = x.shape[0], x.shape[1], x.shape[2], x.shape[3]
     d.Ci, d.Co, d.ksize = ci, co, k
     d.det = _det()
+    d.mfma_bf16 = bf if k == 3 else 0
     return d
 
 
@@ -204,7 +233,8 @@ class _Conv3dHip(torch.autograd.Function):
             xin = F.pad(xin, (0, cip - ci))
         xin = xin.contiguous()
         y = torch.empty(x.shape[:-1] + (co,), device=x.device, dtype=torch.float32)
-        d = _desc(xin, cip, co, k)
+        ctx.bf = _bf16() if k == 3 else 0       # operand mode of this node: its backward uses the same
+        d = _desc(xin, cip, co, k, ctx.bf)
         _lib.check(L.stpde_conv3d_fwd(C.byref(d), _lib.ptr(xin), _lib.ptr(fpack),
                                       _lib.ptr(bias.detach().contiguous()) if bias is not None else None,
                                       _lib.ptr(y), _lib.stream_ptr()))
@@ -224,7 +254,7 @@ class _Conv3dHip(torch.autograd.Function):
         ready = torch.cuda.current_stream().record_event() if ctx.defer is not None else None   # gy is complete here
         if ctx.needs_input_grad[0]:
             dxp = torch.empty(xin.shape, device=gy.device, dtype=torch.float32)
-            d = _desc(gy, co, cip, k)
+            d = _desc(gy, co, cip, k, ctx.bf)
             bpack = wsaved if bidx is None else wsaved[bidx]
             _lib.check(L.stpde_conv3d_fwd(C.byref(d), _lib.ptr(gy), _lib.ptr(bpack), None, _lib.ptr(dxp),
                                           _lib.stream_ptr()))
@@ -241,7 +271,7 @@ class _Conv3dHip(torch.autograd.Function):
                 if ctx.needs_input_grad[1]:
                     # (the bias gradient = column sums of gy comes out of the same kernel: dball is zero-filled per step)
                     dwt, ctx.dwbuf = ctx.dwbuf, None
-                    d = _desc(xin, cip, co, k)
+                    d = _desc(xin, cip, co, k, ctx.bf)
                     _lib.check(L.stpde_conv3d_wgrad_bias(C.byref(d), _lib.ptr(xin), _lib.ptr(gy), _lib.ptr(dwt),
                                                          _lib.ptr(defer.bias_slice(idx)) if want_b else None,
                                                          _lib.stream_ptr()))
@@ -254,7 +284,7 @@ class _Conv3dHip(torch.autograd.Function):
             dwt, ctx.dwbuf = ctx.dwbuf, None     # zero-filled slice of the per-step buffer (used once), else a fresh one
             if dwt is None:
                 dwt = _acc_zeros(ntap * co * cip, gy.device)
-            d = _desc(xin, cip, co, k)
+            d = _desc(xin, cip, co, k, ctx.bf)
             if has_bias and ctx.needs_input_grad[2]:
                 db = _acc_zeros(co, gy.device)     # column sums of gy, from the same kernel
             _lib.check(L.stpde_conv3d_wgrad_bias(C.byref(d), _lib.ptr(xin), _lib.ptr(gy), _lib.ptr(dwt), _lib.ptr(db),
@@ -552,12 +582,14 @@ class _ResBlockHip(torch.autograd.Function):
             stat.append(torch.empty(2 * c, device=dev))
         rm = [bn.running_mean if bn.track_running_stats else None for bn in bns]
         rv = [bn.running_var if bn.track_running_stats else None for bn in bns]
+        ctx.bf = _bf16()                      # operand mode of conv2 (3x3x3), for the forward and the backward of this node
 
         def conv_args(ci_, co_, k):
             a = _lib.Conv3dFusedArgs()
             a.d.B, a.d.T, a.d.Z, a.d.X = shp
             a.d.Ci, a.d.Co, a.d.ksize = ci_, co_, k
             a.d.det = _det()
+            a.d.mfma_bf16 = ctx.bf if k == 3 else 0
             return a
 
         def bn_desc(c, relu, bn):
@@ -636,6 +668,7 @@ class _ResBlockHip(torch.autograd.Function):
             a.d.B, a.d.T, a.d.Z, a.d.X = shp
             a.d.Ci, a.d.Co, a.d.ksize = ci_, co_, k
             a.d.det = _det()
+            a.d.mfma_bf16 = ctx.bf if k == 3 else 0
             return a
 
         def bn_desc(c, relu, k, reduce_done):
@@ -714,6 +747,7 @@ class _ResBlockHip(torch.autograd.Function):
             cd.B, cd.T, cd.Z, cd.X = shp
             cd.Ci, cd.Co, cd.ksize = ci_, co_, ks
             cd.det = _det()
+            cd.mfma_bf16 = ctx.bf if ks == 3 else 0
 
             def launch(dwt, dbt):
                 if onload:

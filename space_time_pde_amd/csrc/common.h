@@ -602,9 +602,16 @@ __device__ __forceinline__ f32x4 row_sum16x4(f32x4 v) {
 // ("window") with an integer atomic -- whatever the order, the K windows end up holding the same integers, and det_value()
 // turns them into the same floating-point number.  Window j weighs 2^(STPDE_DET_BASE + 32 j); a window takes 2^31 pieces before
 // it can overflow.  Range: bit positions 2^-110 ... 2^+81 (values up to ~2^80; magnitudes below 2^-86 (float) / 2^-57 (double)
-// lose their lowest bits -- truncated the same way every time).  A non-finite value poisons the top window (-> NaN).
+// lose their lowest bits -- truncated the same way every time).
+// A non-finite value, or one too large for the windows, MARKS the accumulator: an atomic MAX of the signed top window with
+// 2^62, and det_value() reads a top window at or beyond +-2^61 as NaN.  The mark is idempotent -- any number of marks, in any
+// order with the additions, leaves the top window at 2^62 plus the pieces added after the first mark (each below 2^32, so it
+// takes 2^29 of them, a sum beyond 2^110, to get back under 2^61).  It used to be an atomic ADD of 2^62: four marks summed to
+// 2^64 = 0, and the persistent grids add one partial per workgroup (256 ... 1024 of them), so "every partial is NaN" read back as
+// a finite sum (tests/test_det_accumulator_model.py, tests/test_gpu_det_nonfinite.py).
 // Layout: accumulator e of an array = windows [e * STPDE_DET_K ... + K); the caller zero-fills.
 #define STPDE_DET_BASE (-110)      // (STPDE_DET_K = 6 windows: include/stpde_hip.h)
+__device__ __forceinline__ void det_mark(long long* acc) { atomicMax(acc + STPDE_DET_K - 1, 1ll << 62); }
 __device__ __forceinline__ void det_add_pieces(long long* acc, unsigned long long m, int shift, bool neg) {
   // |value| = m * 2^(BASE + shift), m < 2^53
   if (shift < 0) {
@@ -616,8 +623,8 @@ __device__ __forceinline__ void det_add_pieces(long long* acc, unsigned long lon
   const unsigned long long hi = r ? (m >> (64 - r)) : 0ull;     // bits 64 .. of m << r (< 2^21)
   unsigned long long p0 = lo64 & 0xffffffffull, p1 = lo64 >> 32, p2 = hi;
   if (j >= STPDE_DET_K || (p1 && j + 1 >= STPDE_DET_K) || (p2 && j + 2 >= STPDE_DET_K)) {
-    // too large for the windows (>= 2^70): poison the top window (-> NaN at read-out)
-    atomicAdd(reinterpret_cast<unsigned long long*>(acc + STPDE_DET_K - 1), 1ull << 62);
+    // too large for the windows (the top one weighs 2^50 and takes pieces below 2^32: |value| >= 2^82): mark (-> NaN at read-out)
+    det_mark(acc);
     return;
   }
   if (neg) {
@@ -634,7 +641,7 @@ __device__ __forceinline__ void det_add_f32(long long* acc, float v) {
   const unsigned b = __float_as_uint(v);
   const int ex = (b >> 23) & 0xff;
   if (ex == 0xff) {
-    atomicAdd(reinterpret_cast<unsigned long long*>(acc + STPDE_DET_K - 1), 1ull << 62);
+    det_mark(acc);
     return;
   }
   const unsigned long long m = ex ? ((b & 0x7fffffu) | 0x800000u) : (b & 0x7fffffu);
@@ -646,7 +653,7 @@ __device__ __forceinline__ void det_add_f64(long long* acc, double v) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(v);
   const int ex = (int)((b >> 52) & 0x7ff);
   if (ex == 0x7ff) {
-    atomicAdd(reinterpret_cast<unsigned long long*>(acc + STPDE_DET_K - 1), 1ull << 62);
+    det_mark(acc);
     return;
   }
   const unsigned long long m = ex ? ((b & 0xfffffffffffffull) | 0x10000000000000ull) : (b & 0xfffffffffffffull);

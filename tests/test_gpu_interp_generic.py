@@ -160,7 +160,8 @@ def test_full_size_step_subset_vs_oracle_and_additivity(hiplib, prec, grid, monk
     mode's 3e-2 Frobenius bound; VERDICT r3 #1b: the bf16 mode also on BASELINE configs[3]'s OWN latent grid
     [1,64,256,256,32] = 512 MiB.)  BASELINE configs[1] / [3] size (2^20 points, RB2 + continuity, softplus):
     (a) points are independent, so pred / residuals of a random subset must equal the CPU oracle run on just that subset;
-    (b) gradients are additive over points: grads(all points) == grads(first half) + grads(second half)."""
+    (b) gradients are additive over points: grads(all points) == grads(first half) + grads(second half).
+    Element-wise gradients of the same full-size step against the oracle: tests/test_gpu_full_size_gradients.py."""
     from oracle import cpu_ref
     from space_time_pde_amd import implicit_net, lig_jet, local_implicit_grid as lig, physics
     monkeypatch.setattr(lig_jet, "mlp_precision", prec)
@@ -221,7 +222,8 @@ def test_config5_full_size_properties(hiplib):
     the [1,32,128,128,32] grid, ImNet nf = 32, through whichever of stash / recomputation the memory plan picks:
     (a) a random subset of the points equals the oracle's reverse-sweep autograd on just that subset;
     (b) chunk invariance: one 2^20-point launch chunk and 2^18-point chunks give bit-identical jets;
-    (c) gradients are additive over the points: grads(all) == grads(first half) + grads(second half)."""
+    (c) gradients are additive over the points: grads(all) == grads(first half) + grads(second half).
+    Element-wise gradients of the same full-size step against the oracle: tests/test_gpu_full_size_gradients.py."""
     import bench
     from oracle import cpu_ref as O
     from space_time_pde_amd import _lib, implicit_net, lig_jet, local_implicit_grid as lig, pde

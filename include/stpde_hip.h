@@ -589,6 +589,57 @@ typedef struct {
 int stpde_clip_adam_multi(const stpde_adam_desc* d, const stpde_adam_tensor* tensors_dev,
                           const stpde_adam_chunk* chunks_dev, int nchunks, int chunk_elems, void* stream);
 
+/* ---- capturable optimizers: step count and learning rate in device memory ----------------------------------
+ * A launch captured in a HIP graph freezes its by-value arguments, so an optimizer that is to be replayed keeps what
+ * changes from step to step in a block of device memory the caller owns: 32 bytes, 16-byte aligned, zero-filled before
+ * the first step.  The caller writes `lr` (and `step` when it resumes from a checkpoint); stpde_opt_advance writes
+ * the rest.  The layout is part of the ABI (callers poke the fields through typed views of the block): `step` is a
+ * 64-bit signed integer at byte 0 (`long` on the LP64 targets this library builds for), `lr` an fp64 at byte 8,
+ * `step_size` / `bias2_sqrt` fp32 at bytes 16 / 20; stpde_version() changes with it. */
+typedef struct {
+  long step;                    /* optimizer steps taken (all tensors of a group share it) */
+  double lr;                    /* learning rate (the SGD kernels round it to fp32, like a by-value float) */
+  float step_size, bias2_sqrt;  /* Adam: lr / (1 - beta1^step), sqrt(1 - beta2^step), fp64 rounded to fp32 */
+  float reserved[2];
+} stpde_opt_state;
+typedef struct {
+  double beta1, beta2;          /* Adam's betas; 0, 0 for SGD (step_size = lr, bias2_sqrt = 1) */
+} stpde_opt_desc;
+/* One-workgroup kernel, launched in front of the update kernel of a step: ++step, then the two derived scalars. */
+int stpde_opt_advance(const stpde_opt_desc* d, stpde_opt_state* state_dev, void* stream);
+/* stpde_clip_adam / stpde_clip_adam_multi with step_size and bias2_sqrt read from the state block (d->step_size,
+ * d->bias2_sqrt and the two fields of the table rows are ignored).  The tables hold nothing that changes from step to
+ * step: build them once, reuse them while the pointers stay. */
+int stpde_clip_adam_dev(const stpde_adam_desc* d, const stpde_opt_state* state_dev, float* param, const float* grad,
+                        float* exp_avg, float* exp_avg_sq, void* stream);
+int stpde_clip_adam_multi_dev(const stpde_adam_desc* d, const stpde_opt_state* state_dev,
+                              const stpde_adam_tensor* tensors_dev, const stpde_adam_chunk* chunks_dev, int nchunks,
+                              int chunk_elems, void* stream);
+
+/* ---- gradient value clipping + SGD in one pass (the reference's --optim sgd, train.py:220, :330-333) -------
+ * g = clamp(grad, +-clip) (clip <= 0: off), then torch.optim.SGD: g += weight_decay * p; with momentum != 0
+ * buf = g on the first step, else momentum * buf + (1 - dampening) * g, and g = g + momentum * buf (nesterov) or buf;
+ * p -= lr * g.  state_dev == NULL: lr and first_step of the descriptor (the table row in the multi variant) are used.
+ * state_dev != NULL: lr is the block's, and the step is the first one when the block's count is 1, i.e. right behind
+ * the first stpde_opt_advance.  momentum == 0: no buffer is read or written (momentum_buf / buf may be NULL). */
+typedef struct {
+  long n;
+  float clip, lr, momentum, dampening, weight_decay;
+  int nesterov, first_step;
+} stpde_sgd_desc;
+int stpde_clip_sgd(const stpde_sgd_desc* d, const stpde_opt_state* state_dev, float* param, const float* grad,
+                   float* momentum_buf, void* stream);
+typedef struct {
+  float* p;
+  const float* g;
+  float* buf;
+  long n;
+  int first_step, pad;
+} stpde_sgd_tensor;
+/* All tensors in one launch; chunk table as for stpde_clip_adam_multi (d->n and d->first_step are ignored). */
+int stpde_clip_sgd_multi(const stpde_sgd_desc* d, const stpde_opt_state* state_dev, const stpde_sgd_tensor* tensors_dev,
+                         const stpde_adam_chunk* chunks_dev, int nchunks, int chunk_elems, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

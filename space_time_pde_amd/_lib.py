@@ -19,7 +19,7 @@ _SOURCES = ["jet_layer.hip", "jet_layer_s00.hip", "jet_layer_s03.hip", "jet_laye
 _HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics",
              "--offload-compress"]
 
-ABI_VERSION = 315   # == stpde_version() of the library these ctypes signatures were written for (csrc/api.cpp)
+ABI_VERSION = 316   # == stpde_version() of the library these ctypes signatures were written for (csrc/api.cpp)
 
 ACT_CODES = {"tanh": 0, "relu": 1, "softplus": 2, "elu": 3, "swish": 4, "leakyrelu": 5}
 PBAR_SLOTS = 64   # STPDE_PBAR_SLOTS: accumulation slots of the swish-beta adjoint
@@ -105,6 +105,20 @@ class BnDesc(C.Structure):
 class AdamDesc(C.Structure):
     _fields_ = [("n", C.c_long), ("clip", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("weight_decay", C.c_float), ("step_size", C.c_float), ("bias2_sqrt", C.c_float)]
+
+
+class OptState(C.Structure):        # stpde_opt_state: 32 bytes of device memory, 16-byte aligned
+    _fields_ = [("step", C.c_long), ("lr", C.c_double), ("step_size", C.c_float), ("bias2_sqrt", C.c_float),
+                ("reserved", C.c_float * 2)]
+
+
+class OptDesc(C.Structure):
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double)]
+
+
+class SgdDesc(C.Structure):
+    _fields_ = [("n", C.c_long), ("clip", C.c_float), ("lr", C.c_float), ("momentum", C.c_float), ("dampening", C.c_float),
+                ("weight_decay", C.c_float), ("nesterov", C.c_int), ("first_step", C.c_int)]
 
 
 class InterpDesc(C.Structure):
@@ -244,6 +258,11 @@ _SIGNATURES = {
     "stpde_loss_grad": ([C.c_int, C.c_long, _VP, _VP, _VP, _VP, _VP], C.c_int),
     "stpde_clip_adam": ([C.POINTER(AdamDesc)] + [_VP] * 5, C.c_int),
     "stpde_clip_adam_multi": ([C.POINTER(AdamDesc), _VP, _VP, C.c_int, C.c_int, _VP], C.c_int),
+    "stpde_opt_advance": ([C.POINTER(OptDesc), _VP, _VP], C.c_int),
+    "stpde_clip_adam_dev": ([C.POINTER(AdamDesc)] + [_VP] * 6, C.c_int),
+    "stpde_clip_adam_multi_dev": ([C.POINTER(AdamDesc), _VP, _VP, _VP, C.c_int, C.c_int, _VP], C.c_int),
+    "stpde_clip_sgd": ([C.POINTER(SgdDesc)] + [_VP] * 5, C.c_int),
+    "stpde_clip_sgd_multi": ([C.POINTER(SgdDesc), _VP, _VP, _VP, C.c_int, C.c_int, _VP], C.c_int),
 }
 
 

@@ -238,18 +238,44 @@ class GraphedStep:
     precision of the U-Net's 3x3x3 convolutions (``unet3d.conv_precision``): a graph keeps the mode it was captured with.
 
     Inputs are copied into static buffers before each replay; ``.grad`` of every parameter is a static tensor of the graph's
-    memory pool, rewritten by each replay (the optimizer step runs outside the graph, on those tensors).  Not for a
-    distributed step (collectives are not captured here): ``distributed`` is forced off.
+    memory pool, rewritten by each replay (``self.grads`` keeps them).  Not for a distributed step (collectives are not captured
+    here): ``distributed`` is forced off.
 
         step = GraphedStep(unet, imnet, layer, crop, pts, tgt, n_points_global)
         loss, reg, pde = step(crop2, pts2, tgt2)        # device scalars, valid until the next replay
+
+    ``optimizer=None``: the optimizer step runs outside the graph, on the static gradient tensors -- and an
+    ``optimizer.zero_grad()`` between replays takes them away from it.  ``optimizer=opt`` (a capturable one:
+    ``optim.FusedClipAdam`` / ``FusedClipSGD`` with ``capturable=True``): the optimizer step is captured right behind the
+    backward, so ONE replay is the whole iteration -- forward, backward, clip, update.  It reads the static gradients by address:
+    ``zero_grad()`` or ``p.grad = None`` between replays cannot starve it.  ``group["lr"]`` is pushed to the device before each
+    replay when it changed, so a scheduler needs no re-capture.  ``opt.prepare()`` runs first (flat mode re-points ``p.data``
+    before any address is recorded).  The warm-up has to run optimizer steps too (their kernels must be loaded before the
+    capture), but construction does not train: parameters, optimizer state and step count are snapshotted on the device before
+    the warm-up and restored after it, bit for bit.
+
+        opt = FusedClipAdam(params, lr=1e-2, clip_grad=1.0, capturable=True)
+        step = GraphedStep(unet, imnet, layer, crop, pts, tgt, n_points_global, optimizer=opt)
+        loss, reg, pde = step(crop2, pts2, tgt2)        # parameters already updated
     """
 
     def __init__(self, unet, imnet, pde_layer, input_grid, point_coord, point_value, n_points_global, alpha_reg=1.0,
-                 alpha_pde=1.0, loss_type="l1", xmin=0.0, xmax=1.0, warmup=2):
+                 alpha_pde=1.0, loss_type="l1", xmin=0.0, xmax=1.0, warmup=2, optimizer=None):
+        if optimizer is not None and not (getattr(optimizer, "capturable", False) and all(
+                hasattr(optimizer, m) for m in ("prepare", "state_tensors", "sync_lr", "flush_tables"))):
+            raise ValueError("GraphedStep(optimizer=...) needs a capturable optimizer of this package (FusedClipAdam / "
+                             "FusedClipSGD with capturable=True): it drives the optimizer through prepare() / state_tensors() / "
+                             "sync_lr() / flush_tables(), and a step with host-side scalars would be frozen by the capture")
         if not input_grid.is_cuda:
             raise RuntimeError("GraphedStep needs CUDA/HIP tensors")
+        self.optimizer = optimizer
         self.params = [p for m in (unet, imnet) for p in m.parameters()]
+        snapshot = None
+        if optimizer is not None:
+            optimizer.prepare()
+            with torch.no_grad():
+                live = [p.data for p in self.params] + optimizer.state_tensors()
+                snapshot = (live, [t.clone() for t in live])
         self.static = [t.detach().clone() for t in (input_grid, point_coord, point_value)]
         args = (unet, imnet, pde_layer) + tuple(self.static) + (n_points_global, alpha_reg, alpha_pde, loss_type, xmin, xmax)
 
@@ -260,6 +286,8 @@ class GraphedStep:
             # the layer's forward method closes over this step's latent grid, i.e. over its whole autograd graph: dropped, or
             # the graph -- and the parameters' AccumulateGrad nodes with it -- outlives the step
             pde_layer.forward_method = None
+            if optimizer is not None:
+                optimizer.step()
             return out
 
         # Steps that ran BEFORE this constructor on the default stream leave exactly that behind (pde_layer.forward_method ->
@@ -283,6 +311,9 @@ class GraphedStep:
             for _ in range(max(1, warmup)):
                 run()
         cur.wait_stream(side)
+        if snapshot is not None:         # the warm-up trained: back to the state the caller handed over
+            with torch.no_grad():
+                torch._foreach_copy_(*snapshot)
         torch.cuda.synchronize(input_grid.device)
         for p in self.params:
             p.grad = None
@@ -291,12 +322,17 @@ class GraphedStep:
         # mode refuses although it touches no stream
         with torch.cuda.graph(self.graph, capture_error_mode="relaxed"):
             self.out = run()
+        self.grads = [p.grad for p in self.params]
+        if optimizer is not None:
+            optimizer.flush_tables()     # pointer tables staged during the capture (nothing is uploaded inside one)
         self.replays = 0
 
     def __call__(self, input_grid=None, point_coord=None, point_value=None):
         for dst, src in zip(self.static, (input_grid, point_coord, point_value)):
             if src is not None and src.data_ptr() != dst.data_ptr():
                 dst.copy_(src, non_blocking=True)
+        if self.optimizer is not None:
+            self.optimizer.sync_lr()
         self.graph.replay()
         self.replays += 1
         return self.out

@@ -640,6 +640,70 @@ typedef struct {
 int stpde_clip_sgd_multi(const stpde_sgd_desc* d, const stpde_opt_state* state_dev, const stpde_sgd_tensor* tensors_dev,
                          const stpde_adam_chunk* chunks_dev, int nchunks, int chunk_elems, void* stream);
 
+/* ---- N3 on the device: training batches drawn and produced by capturable launches -------------------------------
+ * Replaces, for lres_filter = 'none', what RB2DataLoader.__getitem__ + RandomSampler(replacement=True) + the collate do per
+ * batch (experiments/rb2d/dataloader_spacetime.py:118-171, train.py:318-321): random crop positions, random query points,
+ * the linearly (or nearest-) down-sampled low-resolution input grid and the interpolated point targets, normalised.
+ * The dataset stays where it is -- data_cl [T][Z][X][4] fp32, channels-last, 16-byte aligned -- and is read in place: no
+ * [B][nt][nz][nx][4] crop is materialised.  Nothing here allocates or synchronises, so both entries are legal inside a
+ * stream capture; what changes from draw to draw lives in a state block of device memory, as for the optimizers.
+ *
+ * State block: 32 bytes of device memory the caller owns, 16-byte aligned.  The layout is part of the ABI (callers fill
+ * and read the fields through a typed view): the Philox key `seed`, an unsigned 64-bit integer at byte 0; the draw
+ * counter `offset`, an unsigned 64-bit integer at byte 8 (one draw = one batch = +1); `oob`, an unsigned 32-bit count at
+ * byte 16 of the crop ids outside [0, len) that the produce entry has clamped so far; 12 reserved bytes.
+ *
+ * Generator: Philox4x32-10 (Salmon et al., SC'11; the Random123 constants).  key = (seed_lo, seed_hi); the 128-bit
+ * counter of a call is (offset_lo, offset_hi, q, purpose): `purpose` selects the stream, q numbers the calls within it.
+ *   purpose 0, crop ids:     word j of call q is crop 4q + j;  id = (word * len) >> 32  (64-bit product), len = rt*rz*rx.
+ *                            Uniform with replacement; an id's probability differs from 1/len by at most 2^-32, i.e. a
+ *                            relative bias of at most len / 2^32 (len < 2^31 is required).
+ *   purpose 1, coordinates:  flat element e = (b*N + n)*3 + k of point_coord is word e % 4 of call e / 4;
+ *                            value = (word >> 8) * 2^-24, exact in fp32, in [0, 1).
+ * Two draws never share a counter as long as `offset` differs, whatever B and N are.
+ *
+ * Arithmetic of the produce entry: bit-identical to RB2DeviceLoader.get() of this package on the same ids and points.
+ *   low-res voxel, linear:   the eight values at taps (i0, i0 + 1) per axis are reduced t first, then z, then x, each stage
+ *                            lo + (hi - lo) * w with every intermediate rounded to fp32; then (v - mean) / std.
+ *   targets, linear:         q = point_coord * (n - 1) per component, then the clip / cell index / corner weights / corner sum
+ *                            of stpde_interp_fwd (csrc/interp_geom.h is shared by both) on the crop's window; then normalise.
+ *   nearest:                 the low-res tap tables hold the node itself (w is ignored); a target takes node i + 1 when
+ *                            q - i > 0.5 with i = min(max(floor(q), 0), n - 2), else node i (ties go down).
+ * Crop origin of id: t0 = id / (rz*rx), z0 = (id / rx) % rz, x0 = id % rx (C-order meshgrid, reference :82-86).  An id
+ * outside [0, len) is clamped into the range before any address is formed and counted in `oob`; tap indices and cell
+ * indices are clamped to the crop as well, so no buffer content can make the kernel read outside data_cl. */
+typedef struct {
+  unsigned long seed;    /* Philox key                                  */
+  unsigned long offset;  /* draws taken so far                          */
+  unsigned int oob;      /* out-of-range explicit crop ids seen so far  */
+  unsigned int reserved[3];
+} stpde_sampler_state;
+typedef struct {
+  int i0;   /* linear: lower tap, in [0, n - 2]; nearest: the node, in [0, n - 1] */
+  float w;  /* linear: weight of tap i0 + 1, fp32 of an fp64 host computation      */
+} stpde_sampler_tap;
+typedef struct {
+  int T, Z, X;           /* dataset extents                                        */
+  int nt, nz, nx;        /* crop extents (>= 2 each)                               */
+  int ntl, nzl, nxl;     /* low-res extents; each divides its crop extent          */
+  int rt, rz, rx;        /* crop ranges: T - nt + 1, Z - nz + 1, X - nx + 1        */
+  int B, N;              /* crops per batch, points per crop                       */
+  int interp;            /* 0 linear, 1 nearest                                    */
+  int normalize;         /* 1: (v - mean[c]) / std[c] on both outputs              */
+  float mean[4], std[4];
+  float lo_c[3], hi_c[3], cube[3]; /* as stpde_interp_desc for the crop box [0, n - 1] */
+} stpde_sampler_desc;
+/* crop_idx_out [B] int32, point_coord_out [B][N][3] fp32; then offset += 1 by a one-thread kernel behind the draw kernel
+ * in stream order (never a race with the reads of `offset`). */
+int stpde_sampler_draw(const stpde_sampler_desc* d, stpde_sampler_state* state_dev, int* crop_idx_out,
+                       float* point_coord_out, void* stream);
+/* One launch: lres_out [B][4][ntl][nzl][nxl], point_value_out [B][N][4].  crop_idx / point_coord: what the draw entry
+ * filled, or the caller's own (explicit mode). */
+int stpde_sampler_produce(const stpde_sampler_desc* d, stpde_sampler_state* state_dev, const float* data_cl,
+                          const stpde_sampler_tap* taps_t, const stpde_sampler_tap* taps_z,
+                          const stpde_sampler_tap* taps_x, const int* crop_idx, const float* point_coord,
+                          float* lres_out, float* point_value_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

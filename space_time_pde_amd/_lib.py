@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 # STPDE_LIB: load another build of the library (A/B timing of kernel variants on one box; never set by tests or the driver)
 LIB_PATH = os.environ.get("STPDE_LIB") or os.path.join(_HERE, "libstpde_hip.so")
-_SOURCES = ["jet_layer.hip", "jet_layer_s00.hip", "jet_layer_s03.hip", "jet_layer_s30.hip", "jet_layer_s31.hip", "jet_layer_s32.hip", "jet_layer_s34.hip", "jet_layer_s36.hip", "jet_tail.hip", "jet_wgrad.hip", "jet_wgrad_s00.hip", "jet_wgrad_s30.hip", "jet_wgrad_s31.hip", "jet_wgrad_s32.hip", "jet_wgrad_s34.hip", "jet_wgrad_s36.hip", "jet_fc1_bwd.hip", "lig_gather_reduce.hip", "lig_pipeline.hip", "interp_nd.hip", "conv3d.hip", "conv3d_fused.hip", "optim.hip", "residual.hip", "bn.hip", "resample.hip", "api.cpp"]
+_SOURCES = ["jet_layer.hip", "jet_layer_s00.hip", "jet_layer_s03.hip", "jet_layer_s30.hip", "jet_layer_s31.hip", "jet_layer_s32.hip", "jet_layer_s34.hip", "jet_layer_s36.hip", "jet_tail.hip", "jet_wgrad.hip", "jet_wgrad_s00.hip", "jet_wgrad_s30.hip", "jet_wgrad_s31.hip", "jet_wgrad_s32.hip", "jet_wgrad_s34.hip", "jet_wgrad_s36.hip", "jet_fc1_bwd.hip", "lig_gather_reduce.hip", "lig_pipeline.hip", "interp_nd.hip", "conv3d.hip", "conv3d_fused.hip", "optim.hip", "residual.hip", "bn.hip", "resample.hip", "sampler.hip", "api.cpp"]
 # --offload-compress: the gfx950 code objects are stored zstd-compressed in the fat binary (the HIP runtime inflates them at
 # module load): libstpde_hip.so 68 MB -> ~1/4; the instruction bytes are the same (tools/check_dpp_hazard.py scans them)
 _HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics",
@@ -124,6 +124,21 @@ class SgdDesc(C.Structure):
 class InterpDesc(C.Structure):
     _fields_ = [("P", C.c_int), ("N", C.c_int), ("B", C.c_int), ("dim", C.c_int), ("C", C.c_int),
                 ("n", C.c_int * 4), ("lo_c", C.c_float * 4), ("hi_c", C.c_float * 4), ("cube", C.c_float * 4)]
+
+
+class SamplerState(C.Structure):    # stpde_sampler_state: 32 bytes of device memory, 16-byte aligned
+    _fields_ = [("seed", C.c_ulong), ("offset", C.c_ulong), ("oob", C.c_uint), ("reserved", C.c_uint * 3)]
+
+
+class SamplerTap(C.Structure):
+    _fields_ = [("i0", C.c_int), ("w", C.c_float)]
+
+
+class SamplerDesc(C.Structure):
+    _fields_ = [("T", C.c_int), ("Z", C.c_int), ("X", C.c_int), ("nt", C.c_int), ("nz", C.c_int), ("nx", C.c_int),
+                ("ntl", C.c_int), ("nzl", C.c_int), ("nxl", C.c_int), ("rt", C.c_int), ("rz", C.c_int), ("rx", C.c_int),
+                ("B", C.c_int), ("N", C.c_int), ("interp", C.c_int), ("normalize", C.c_int), ("mean", C.c_float * 4),
+                ("std", C.c_float * 4), ("lo_c", C.c_float * 3), ("hi_c", C.c_float * 3), ("cube", C.c_float * 3)]
 
 
 def _sources():
@@ -263,6 +278,8 @@ _SIGNATURES = {
     "stpde_clip_adam_multi_dev": ([C.POINTER(AdamDesc), _VP, _VP, _VP, C.c_int, C.c_int, _VP], C.c_int),
     "stpde_clip_sgd": ([C.POINTER(SgdDesc)] + [_VP] * 5, C.c_int),
     "stpde_clip_sgd_multi": ([C.POINTER(SgdDesc), _VP, _VP, _VP, C.c_int, C.c_int, _VP], C.c_int),
+    "stpde_sampler_draw": ([C.POINTER(SamplerDesc)] + [_VP] * 4, C.c_int),
+    "stpde_sampler_produce": ([C.POINTER(SamplerDesc)] + [_VP] * 10, C.c_int),
 }
 
 

@@ -2,7 +2,7 @@
 // regular_nd_grid_interpolation / ..._coefficients (src/regular_nd_grid_interpolation.py:14-104) and the
 // scatter-add backward of its gather (:65-66).  HBM/L2-bound gather: one thread per (point, channel), lanes
 // run along the channel axis so each corner read is a contiguous C*4-byte segment.
-#include "common.h"
+#include "interp_geom.h"
 
 struct InterpArgs {
   stpde_interp_desc d;
@@ -17,29 +17,13 @@ struct InterpArgs {
   float* dgrid;
 };
 
-struct GeomN {
-  float om[2][4], rl[2][4];
-  int i0[4];
-};
-
 __device__ __forceinline__ GeomN geom_nd(const InterpArgs& a, int p) {
   GeomN gm;
   const int dim = a.d.dim;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     if (k < dim) {
-      const float x = a.pts[(size_t)p * dim + k];
-      const float q = fmaxf(fminf(x, a.d.hi_c[k]), a.d.lo_c[k]);
-      const float cs = a.d.cube[k];
-      int i0 = (int)floorf(q / cs);
-      i0 = i0 < 0 ? 0 : (i0 > a.d.n[k] - 2 ? a.d.n[k] - 2 : i0);
-      const float i0f = (float)i0;
-      const float p0 = i0f * cs, p1 = (i0f + 1.f) * cs;
-      gm.i0[k] = i0;
-      gm.om[0][k] = fabsf(q - p1) / cs;
-      gm.om[1][k] = fabsf(q - p0) / cs;
-      gm.rl[0][k] = (q - p0) / cs;
-      gm.rl[1][k] = (q - p1) / cs;
+      geom_axis(gm, k, a.pts[(size_t)p * dim + k], a.d.lo_c[k], a.d.hi_c[k], a.d.cube[k], a.d.n[k]);
     } else {
       gm.i0[k] = 0;
       gm.om[0][k] = gm.om[1][k] = 1.f;
@@ -62,15 +46,13 @@ __global__ __launch_bounds__(256) void k_interp(InterpArgs a) {
   const float ob = (BWD && a.out_bar) ? a.out_bar[(size_t)p * C + c] : 0.f;
   for (int j = 0; j < nc; ++j) {
     size_t node = b;
-    float w = 1.f;
+    const float w = corner_weight(gm, j, dim);
     float rl[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (k < dim) {
-        const int bit = (j >> (dim - 1 - k)) & 1;  // first dim most significant (:55-56)
+        const int bit = corner_bit(j, dim, k);
         node = node * a.d.n[k] + gm.i0[k] + bit;
-        const float o = bit ? gm.om[1][k] : gm.om[0][k];
-        w = (k == 0) ? o : w * o;
         rl[k] = bit ? gm.rl[1][k] : gm.rl[0][k];
       }
     }

@@ -9,6 +9,10 @@ reference's constructor signature (:18-21) and ``__getitem__`` tuple (:118-171),
 (none / gaussian / uniform / median / maximum with scipy.ndimage's 'reflect' boundary, :96-116), ``lres_interp``
 (linear / nearest), ``normalize_output`` / ``normalize_hres`` / ``return_hres``.  Both are checked against vectors
 produced by the imported reference loader (tests/golden/n3_dataloader.npz).
+
+``DeviceBatchSampler`` draws whole training batches of an ``RB2DeviceLoader`` on the device with capturable launches
+(csrc/sampler.hip), bit-identical to ``RB2DeviceLoader.get()`` on the same crop ids and points; ``sampler_expected`` is
+its host model.
 """
 import os
 
@@ -211,6 +215,195 @@ class RB2DeviceLoader:
 
     def denormalize_points(self, points):
         return points * self._std.to(points.device) + self._mean.to(points.device)
+
+
+# ---- batches drawn and produced on the device (csrc/sampler.hip) ----------------------------------------------------------
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_M32, _M64 = (1 << 32) - 1, (1 << 64) - 1
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11) on the host, in numpy integers: ``counter`` [..., 4] and ``key`` [..., 2] (uint32
+    values, broadcast against each other) -> [..., 4] uint32 words.  The host model of the device generator."""
+    c = np.array(np.broadcast_arrays(*[np.asarray(counter, dtype=np.uint64)[..., i] for i in range(4)]), dtype=np.uint64)
+    k0, k1 = [np.asarray(key, dtype=np.uint64)[..., i] for i in range(2)]
+    c0, c1, c2, c3 = c
+    m32 = np.uint64(_M32)
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M0) * c0, np.uint64(_PHILOX_M1) * c2        # 32 x 32 -> 64 bits: no overflow in uint64
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(_PHILOX_W0)) & m32, (k1 + np.uint64(_PHILOX_W1)) & m32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def sampler_expected(seed, offset, batch_size, n_points, length):
+    """Host model of ``stpde_sampler_draw``: the crop ids [B] (int32) and point coordinates [B, N, 3] (fp32) that the draw at
+    ``offset`` of the generator seeded with ``seed`` produces for ``length`` crop positions -- the same Philox4x32-10, counter
+    layout (offset_lo, offset_hi, q, purpose) and integer mappings as the kernel (include/stpde_hip.h), in plain numpy."""
+    seed, offset = int(seed) & _M64, int(offset) & _M64
+    if not 0 < int(length) < (1 << 31):
+        raise ValueError("length must be in [1, 2^31)")
+    key = np.array([seed & _M32, seed >> 32], dtype=np.uint64)
+
+    def words(purpose, n):
+        q = np.arange((n + 3) // 4, dtype=np.uint64)
+        ctr = np.stack([np.full_like(q, offset & _M32), np.full_like(q, offset >> 32), q, np.full_like(q, purpose)], axis=-1)
+        return philox4x32_10(ctr, key).reshape(-1)[:n].astype(np.uint64)
+
+    ids = ((words(0, batch_size) * np.uint64(length)) >> np.uint64(32)).astype(np.int32)
+    n = batch_size * n_points * 3
+    coord = (words(1, n) >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)       # 24 bits: exact in fp32
+    return torch.from_numpy(ids), torch.from_numpy(coord.reshape(batch_size, n_points, 3))
+
+
+def _signed64(v):
+    v = int(v) & _M64
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+class DeviceBatchSampler:
+    """Training batches of an ``RB2DeviceLoader`` drawn AND produced on the device by three kernel launches that are legal
+    inside a HIP-graph capture (``stpde_sampler_draw`` / ``stpde_sampler_produce``, csrc/sampler.hip): crop positions (uniform,
+    with replacement, like the reference's ``RandomSampler(replacement=True)``, train.py:318-321) and query points come from a
+    counter-based generator whose state lives in device memory; the low-resolution grid and the interpolated targets are written
+    into static buffers straight from the dataset, bit-identical to ``loader.get()`` on the same ids and points.
+
+        sampler = DeviceBatchSampler(loader, batch_size=10, seed=0)
+        lres, point_coord, point_value = sampler.draw()          # the static buffers, rewritten by every draw
+        ids, pts = sampler.expected(k)                           # host model: what draw number k produced / will produce
+
+    Every buffer a draw touches is allocated here, once: a captured graph replays addresses.  ``GraphedStep(sampler=...)`` puts
+    the draw at the head of every replay.  Loaders with an ``lres_filter`` are refused (``RB2DeviceLoader.get()`` filters)."""
+
+    def __init__(self, loader, batch_size, seed=0):
+        if loader.lres_filter and loader.lres_filter != 'none':
+            raise NotImplementedError("DeviceBatchSampler does not filter (lres_filter=%r): RB2DeviceLoader.get() is the path "
+                                      "that applies the low-res filters" % (loader.lres_filter,))
+        if int(batch_size) <= 0:
+            raise ValueError("batch_size must be positive")
+        if not loader.data_cl.is_cuda:
+            raise RuntimeError("DeviceBatchSampler needs a loader on a HIP device (RB2DeviceLoader(..., device='cuda'))")
+        from . import _lib
+        from .lig_jet import cached_box_constants
+        self.loader, self.batch_size = loader, int(batch_size)
+        dev = loader.data_cl.device
+        B, N = self.batch_size, int(loader.n_samp_pts_per_crop)
+        n = (loader.nt_hres, loader.nz_hres, loader.nx_hres)
+        nl = (loader.nt_lres, loader.nz_lres, loader.nx_lres)
+        d = _lib.SamplerDesc()
+        d.T, d.Z, d.X = loader.data_cl.shape[:3]
+        d.nt, d.nz, d.nx = n
+        d.ntl, d.nzl, d.nxl = nl
+        d.rt, d.rz, d.rx = loader._ranges
+        d.B, d.N = B, N
+        d.interp = 1 if loader.lres_interp == 'nearest' else 0
+        d.normalize = 1 if loader.normalize_output else 0
+        mean, std = loader._mean.tolist(), loader._std.tolist()
+        lo_c, hi_c, cube = cached_box_constants(n, (0., 0., 0.), loader._xmax)      # what get()'s interpolation call uses
+        for c in range(4):
+            d.mean[c], d.std[c] = mean[c], std[c]
+        for k in range(3):
+            d.lo_c[k], d.hi_c[k], d.cube[k] = lo_c[k], hi_c[k], cube[k]
+        self._desc = d
+        # per-axis tap tables [n_lres] of (int32 i0, fp32 w): linear = the loader's own two-tap tables; nearest = the node that
+        # _nearest's rule picks for the loader's own fp32 lattice coordinate (the rule is separable), w unused
+        lattice = loader._lres_coord.reshape(nl + (3,))
+        axes = (lattice[:, 0, 0, 0], lattice[0, :, 0, 1], lattice[0, 0, :, 2])
+        self._taps = []
+        for k in range(3):
+            if d.interp:
+                i = torch.clamp(torch.clamp(torch.floor(axes[k]), min=0).long(), max=n[k] - 2)
+                i0, w = torch.where(axes[k] - i <= 0.5, i, i + 1), torch.zeros(nl[k], device=dev)
+            else:
+                i0, w = loader._lres_taps[k]
+            tab = torch.stack([i0.to(torch.int32), w.to(torch.float32).contiguous().view(torch.int32)], dim=1)
+            self._taps.append(tab.contiguous().to(dev))
+        self.lres = torch.zeros(B, 4, *nl, device=dev)
+        self.point_coord = torch.zeros(B, N, 3, device=dev)
+        self.point_value = torch.zeros(B, N, 4, device=dev)
+        self.crop_idx = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._state = torch.zeros(4, dtype=torch.int64, device=dev)     # stpde_sampler_state: seed, offset, oob | pad, pad
+        self.seed(seed)
+
+    def __len__(self):
+        return len(self.loader)
+
+    # -- state --------------------------------------------------------------------------------------------------------------
+    def seed(self, seed, offset=0):
+        """(Re)start the sequence: Philox key ``seed``, draw counter ``offset``; the out-of-range count is cleared.  Fills on
+        the current stream -- not inside a capture (a replay would reset the counter every time)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("DeviceBatchSampler.seed() inside a stream capture")
+        self._seed = int(seed) & _M64
+        self._state[0].fill_(_signed64(seed))
+        self._state[1].fill_(_signed64(offset))
+        self._state[2:].fill_(0)
+
+    def offset(self):
+        """The draw counter, read back from the device (synchronises)."""
+        return int(self._state[1].item()) & _M64
+
+    def oob_count(self):
+        """Explicit crop ids outside [0, len) that produce() has clamped since the last seed() (synchronises)."""
+        return int(self._state[2].item()) & _M32
+
+    def check(self):
+        """Raise if any explicit crop id was out of range (they are clamped on the device, never followed)."""
+        n = self.oob_count()
+        if n:
+            raise IndexError("DeviceBatchSampler: %d crop id(s) outside [0, %d) were clamped into range" % (n, len(self)))
+
+    def state_dict(self):
+        return {"seed": self._seed, "offset": self.offset()}
+
+    def load_state_dict(self, state):
+        self.seed(state["seed"], state["offset"])
+
+    def expected(self, offset):
+        """Host model: (crop ids [B] int32, point_coord [B, N, 3] fp32), CPU tensors, of the draw at ``offset``."""
+        return sampler_expected(self._seed, offset, self.batch_size, int(self.loader.n_samp_pts_per_crop), len(self))
+
+    # -- launches -----------------------------------------------------------------------------------------------------------
+    def _produce(self, crop_idx, point_coord):
+        import ctypes as C
+        from . import _lib
+        _lib.check(_lib.lib().stpde_sampler_produce(
+            C.byref(self._desc), _lib.ptr(self._state), _lib.ptr(self.loader.data_cl), _lib.ptr(self._taps[0]),
+            _lib.ptr(self._taps[1]), _lib.ptr(self._taps[2]), _lib.ptr(crop_idx), _lib.ptr(point_coord), _lib.ptr(self.lres),
+            _lib.ptr(self.point_value), _lib.stream_ptr()))
+
+    def draw(self):
+        """Next batch: two library calls on the current stream (capturable), no allocation, no synchronisation.  Returns the
+        static (lres [B,4,nt_l,nz_l,nx_l], point_coord [B,N,3], point_value [B,N,4]); ``crop_idx`` holds the ids."""
+        import ctypes as C
+        from . import _lib
+        with _lib.device_of(self._state):
+            _lib.check(_lib.lib().stpde_sampler_draw(C.byref(self._desc), _lib.ptr(self._state), _lib.ptr(self.crop_idx),
+                                                     _lib.ptr(self.point_coord), _lib.stream_ptr()))
+            self._produce(self.crop_idx, self.point_coord)
+        return self.lres, self.point_coord, self.point_value
+
+    def produce(self, crop_idx, point_coord):
+        """Explicit mode: the batch of the given crop ids [B] and points [B, N, 3] in [0, 1] (for parity checks, or a sampling
+        scheme of the caller's own); the generator state does not move.  A host sequence of ids is range-checked here
+        (IndexError); a device tensor is passed through -- the kernel clamps an id outside [0, len) before it forms any
+        address and counts it, see check().  Returns (lres, point_coord, point_value): the static outputs and the given points."""
+        from . import _lib
+        dev = self._state.device
+        if not torch.is_tensor(crop_idx):
+            ids = [int(i) for i in crop_idx]
+            bad = [i for i in ids if not 0 <= i < len(self)]
+            if bad:
+                raise IndexError("crop id %d outside [0, %d)" % (bad[0], len(self)))
+            crop_idx = torch.tensor(ids, dtype=torch.int32, device=dev)
+        crop_idx = crop_idx.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        point_coord = torch.as_tensor(point_coord, dtype=torch.float32).to(dev).contiguous()
+        if crop_idx.numel() != self.batch_size or tuple(point_coord.shape) != tuple(self.point_coord.shape):
+            raise ValueError("produce() needs %d crop ids and points of shape %s" % (self.batch_size,
+                                                                                    tuple(self.point_coord.shape)))
+        with _lib.device_of(self._state):
+            self._produce(crop_idx, point_coord)
+        return self.lres, point_coord, self.point_value
 
 
 class RB2DataLoader(torch.utils.data.Dataset):

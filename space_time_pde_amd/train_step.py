@@ -257,10 +257,27 @@ class GraphedStep:
         opt = FusedClipAdam(params, lr=1e-2, clip_grad=1.0, capturable=True)
         step = GraphedStep(unet, imnet, layer, crop, pts, tgt, n_points_global, optimizer=opt)
         loss, reg, pde = step(crop2, pts2, tgt2)        # parameters already updated
+
+    ``sampler=s`` (a ``dataloader_spacetime.DeviceBatchSampler``): the step draws its own batch.  ``s.draw()`` is the first thing
+    a step does, so the capture holds the draw and the produce kernels in front of the U-Net forward, the static inputs ARE the
+    sampler's output buffers (no copy), and every replay trains on a new batch; inputs are not passed (``None``), passing any is
+    a ``ValueError``.  The warm-up steps draw too (their kernels must be loaded before the capture), but construction consumes no
+    draw: the sampler's state block is snapshotted before the warm-up and restored after it, and a capture executes nothing --
+    replay k (0-based) trains on the draw at ``offset0 + k``, which ``s.expected(offset0 + k)`` reproduces on the host.
+
+        s = DeviceBatchSampler(loader, batch_size=10, seed=0)
+        step = GraphedStep(unet, imnet, layer, None, None, None, n_points_global, optimizer=opt, sampler=s)
+        loss, reg, pde = step()                         # one replay = draw + forward + backward + clip + update
     """
 
     def __init__(self, unet, imnet, pde_layer, input_grid, point_coord, point_value, n_points_global, alpha_reg=1.0,
-                 alpha_pde=1.0, loss_type="l1", xmin=0.0, xmax=1.0, warmup=2, optimizer=None):
+                 alpha_pde=1.0, loss_type="l1", xmin=0.0, xmax=1.0, warmup=2, optimizer=None, sampler=None):
+        if sampler is not None:
+            if input_grid is not None or point_coord is not None or point_value is not None:
+                raise ValueError("GraphedStep(sampler=...) draws its own batches: pass input_grid / point_coord / point_value "
+                                 "as None")
+            input_grid, point_coord, point_value = sampler.lres, sampler.point_coord, sampler.point_value
+        self.sampler = sampler
         if optimizer is not None and not (getattr(optimizer, "capturable", False) and all(
                 hasattr(optimizer, m) for m in ("prepare", "state_tensors", "sync_lr", "flush_tables"))):
             raise ValueError("GraphedStep(optimizer=...) needs a capturable optimizer of this package (FusedClipAdam / "
@@ -276,12 +293,18 @@ class GraphedStep:
             with torch.no_grad():
                 live = [p.data for p in self.params] + optimizer.state_tensors()
                 snapshot = (live, [t.clone() for t in live])
-        self.static = [t.detach().clone() for t in (input_grid, point_coord, point_value)]
+        if sampler is not None:
+            self.static = [input_grid, point_coord, point_value]         # the sampler's own buffers: drawn into, never copied
+            sampler_state = sampler._state.clone()
+        else:
+            self.static = [t.detach().clone() for t in (input_grid, point_coord, point_value)]
         args = (unet, imnet, pde_layer) + tuple(self.static) + (n_points_global, alpha_reg, alpha_pde, loss_type, xmin, xmax)
 
         def run():
             for p in self.params:
                 p.grad = None
+            if sampler is not None:
+                sampler.draw()
             out = sharded_step(*args, distributed=False)
             # the layer's forward method closes over this step's latent grid, i.e. over its whole autograd graph: dropped, or
             # the graph -- and the parameters' AccumulateGrad nodes with it -- outlives the step
@@ -314,6 +337,8 @@ class GraphedStep:
         if snapshot is not None:         # the warm-up trained: back to the state the caller handed over
             with torch.no_grad():
                 torch._foreach_copy_(*snapshot)
+        if sampler is not None:          # the warm-up drew: back to the offset the caller handed over
+            sampler._state.copy_(sampler_state)
         torch.cuda.synchronize(input_grid.device)
         for p in self.params:
             p.grad = None
@@ -328,6 +353,8 @@ class GraphedStep:
         self.replays = 0
 
     def __call__(self, input_grid=None, point_coord=None, point_value=None):
+        if self.sampler is not None and not (input_grid is None and point_coord is None and point_value is None):
+            raise ValueError("this GraphedStep draws its own batches (sampler=...): call it without inputs")
         for dst, src in zip(self.static, (input_grid, point_coord, point_value)):
             if src is not None and src.data_ptr() != dst.data_ptr():
                 dst.copy_(src, non_blocking=True)

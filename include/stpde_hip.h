@@ -389,6 +389,36 @@ int stpde_interp_fwd(const stpde_interp_desc* d, const float* grid, const float*
 int stpde_interp_bwd_grid(const stpde_interp_desc* d, const float* pts, const float* out_bar,
                           const float* corner_bar, float* dgrid, void* stream);
 
+/* ---- a1/a2/a4 for dim = 1, 2, 4: VALUE-ONLY local-implicit-grid queries -------------------------------
+ * The reference states query_local_implicit_grid for [b, n1..nd, c] grids (src/local_implicit_grid.py:10-61; its unit test
+ * runs a 4-d query).  These two calls put such a query on the layer kernels above in their one-stream (value) configuration:
+ *   stpde_lig_gather_nd      clip, cell index, corner gather, relative coordinates -> X [ntiles][3][64][4], the SAME
+ *                            augmented-input image stpde_lig_gather writes, features [r(D) ; latent(C) ; 1] in the same slots
+ *                            (D + C + 1 <= 36), and the corner weights cw [ntiles][16] (one per row)
+ *   stpde_jet_layer_fwd / stpde_jet_tail_fwd_p   unchanged, S1 = S2 = 0 or the value-tile mode, over ntiles row tiles
+ *   stpde_lig_reduce_nd_fwd  y[ch * ldp + p] = sum_j cw[row(p, j)] * out_pre[row(p, j)][ch], fp32, in corner order
+ * A row tile holds 16 >> D points: row j = corner j & (2^D - 1) (first axis most significant, as stpde_interp_fwd) of point
+ * tile * (16 >> D) + (j >> D).  pts [P][D] is a chunk of the [B * N] point list starting at p_base; latent
+ * [B][n_0..n_{D-1}][C] contiguous; lo_c / hi_c / cube as for stpde_lig_gather (xmin must be 0).  ntiles may exceed
+ * ceil(P / (16 >> D)) by up to 3 (the value-tile mode wants a multiple of 4): rows of points >= P are written as zeros
+ * with weight 0 and belong to no output point; nothing is read or written past P points or ntiles tiles.  The cell index
+ * is clamped to [0, n_k - 2] after the float clip and the batch index to B - 1, so no coordinate value -- NaN, infinite,
+ * outside the box -- forms an address outside the latent grid.  No derivative streams and no backward: such requests take
+ * the composed formulation (local_implicit_grid.py).  Refused with STPDE_E_BADARG: D other than 1, 2, 4; P < 1; ntiles
+ * outside [ceil(P / (16 >> D)), that + 3]; an axis with fewer than 2 nodes; D + C + 1 > 36; B * prod(n) or p_base + P
+ * beyond 31 bits; n_out outside 1..16; ldp < P; a null pointer. */
+typedef struct {
+  int D, P, N, B, C;
+  int p_base; /* global index of pts[0]: batch of point p is min((p_base + p) / N, B - 1) */
+  int ntiles;
+  int n[4];
+  float lo_c[4], hi_c[4], cube[4];
+} stpde_gather_nd_desc;
+int stpde_lig_gather_nd(const stpde_gather_nd_desc* d, const float* pts, const float* latent, float* X,
+                        float* cw /* [ntiles][16] */, void* stream);
+int stpde_lig_reduce_nd_fwd(int D, int P, int ntiles, int n_out, const float* out_pre /* fc5 rows [ntiles][64][4] */,
+                            const float* cw, float* y, long ldp, void* stream);
+
 /* ---- a10: 3-D convolution of the U-Net encoder (src/unet3d.py:39-56: nn.Conv3d 1x1x1 and 3x3x3/pad 1, stride 1)
  * Activations are channels-last: x [B][T][Z][X][Ci], y [B][T][Z][X][Co], Ci and Co multiples of 16.
  * Implicit GEMM on v_mfma_f32_16x16x4_f32: y^T[Co x 16 voxels] = sum_tap W_tap[Co x Ci] * x_tap^T[Ci x 16 voxels].

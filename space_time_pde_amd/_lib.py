@@ -37,6 +37,12 @@ class GatherDesc(C.Structure):
                 ("cube", C.c_float * 3), ("alpha", C.c_float * 6)]
 
 
+class GatherNdDesc(C.Structure):        # stpde_gather_nd_desc
+    _fields_ = [("D", C.c_int), ("P", C.c_int), ("N", C.c_int), ("B", C.c_int), ("C", C.c_int), ("p_base", C.c_int),
+                ("ntiles", C.c_int), ("n", C.c_int * 4), ("lo_c", C.c_float * 4), ("hi_c", C.c_float * 4),
+                ("cube", C.c_float * 4)]
+
+
 class LayerDesc(C.Structure):
     _fields_ = [("ntiles", C.c_int), ("KT", C.c_int), ("MT", C.c_int), ("first_hidden", C.c_int), ("cfg", JetCfg),
                 ("mfma_bf16", C.c_int), ("packed", C.c_int), ("det", C.c_int)]
@@ -228,6 +234,8 @@ _SIGNATURES = {
     "stpde_trace_enable": ([C.c_int], C.c_int),
     "stpde_trace_read": ([C.c_char_p, C.c_ulong], C.c_long),
     "stpde_lig_gather": ([C.POINTER(GatherDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP], C.c_int),
+    "stpde_lig_gather_nd": ([C.POINTER(GatherNdDesc), _VP, _VP, _VP, _VP, _VP], C.c_int),
+    "stpde_lig_reduce_nd_fwd": ([C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, C.c_long, _VP], C.c_int),
     "stpde_jet_layer_fwd": ([C.POINTER(LayerDesc)] + [_VP] * 12, C.c_int),
     "stpde_jet_layer_bwd": ([C.POINTER(LayerDesc)] + [_VP] * 13, C.c_int),
     "stpde_jet_layer_bwd_to": ([C.POINTER(LayerDesc)] + [_VP] * 8, C.c_int),

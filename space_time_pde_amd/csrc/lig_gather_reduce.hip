@@ -7,8 +7,9 @@
 //   k_reduce_bwd  its adjoint
 //   k_xbar        d latent: xbar = sum_l W_s,l^T abar_l, scatter-added at the 8 corner nodes (backward of the
 //                 advanced-index gather at src/regular_nd_grid_interpolation.py:65-66)
+//   k_gather_nd / k_reduce_nd   the value-only gather and corner sum for dim = 1, 2, 4 (end of this file)
 // All of these are HBM/L2-bound byte movers; no MFMA except the small xbar GEMM.
-#include "common.h"
+#include "interp_geom.h"
 
 struct PointGeom {
   float om[2][3];   // omega[b][d] = |q_d - pos_opposite| / cube_d
@@ -737,4 +738,189 @@ extern "C" int stpde_lig_dlatent_reduce(int B, int n0, int n1, int n2, int C, co
   const size_t n = (size_t)B * n0 * n1 * n2 * 16;
   STPDE_LAUNCH(k_dlat_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   return stpde_check_launch("k_dlat_reduce");
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// value-only queries on 1-, 2- and 4-d grids (src/local_implicit_grid.py:47-59 for the [b, n1..nd, c] grids the reference
+// states its operator for): gather into the SAME augmented-input image the layer kernels read, and the corner sum
+// ---------------------------------------------------------------------------------------------------------
+// A row tile holds 16 >> D points; row j of a tile = corner (j & (2^D - 1)) of point tile * (16 >> D) + (j >> D), corners in
+// the order of interp_nd.hip (first axis most significant).  Feature f of the augmented input [r(D); latent(C); 1] sits in
+// slot f of tiles 0 / 1 and in register 0 of the sparse third tile (x_live()), as for dim = 3.
+//
+// Addresses.  Every index below is bounded for EVERY input value, not only for points inside the box:
+//   pts     p < P (rows of p >= P are padding: zeros, weight 0, no read), k < D
+//   latent  batch clamped to B - 1, cell index clamped to [0, n_k - 2] by geom_axis() after the float clip (NaN and huge
+//           coordinates end there), corner bit 0 / 1, channel f - D < C: node < B * prod(n), all in 64-bit
+//   X       gid < ntiles * XT * 64 (the grid is derived from ntiles alone), one float4 per thread
+//   cw      tile * 16 + j < ntiles * 16
+struct GatherNdArgs {
+  stpde_gather_nd_desc d;
+  const float* pts;
+  const float* latent;
+  float* X;
+  float* cw;
+};
+
+template <int D>
+__global__ __launch_bounds__(256) void k_gather_nd(GatherNdArgs a) {
+  constexpr int TP = 16 >> D, NC = 1 << D;
+  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (size_t)a.d.ntiles * XT * 64) return;
+  const int lane = gid & 63;
+  const int xt = (gid >> 6) % XT;
+  const size_t tile = (gid >> 6) / XT;
+  const int g = lane >> 4, j = lane & 15;
+  const size_t p = tile * TP + (j >> D);
+  const int corner = j & (NC - 1);
+  f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+  float w = 0.f;
+  if (p < (size_t)a.d.P) {
+    GeomN gm;
+#pragma unroll
+    for (int k = 0; k < D; ++k)
+      geom_axis(gm, k, a.pts[p * D + k], a.d.lo_c[k], a.d.hi_c[k], a.d.cube[k], a.d.n[k]);
+    size_t b = ((size_t)a.d.p_base + p) / (size_t)a.d.N;
+    b = b > (size_t)(a.d.B - 1) ? (size_t)(a.d.B - 1) : b;
+    size_t node = b;
+    w = 1.f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const int bit = corner_bit(corner, D, k);
+      node = node * (size_t)a.d.n[k] + (size_t)(gm.i0[k] + bit);
+      const float o = bit ? gm.om[1][k] : gm.om[0][k];
+      w = (k == 0) ? o : w * o;
+    }
+    const int C = a.d.C;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      // feature held by slot (xt, g, r): tiles 0 / 1 in order, tile 2 sparse (register 0 only: features 32 + g)
+      const int f = xt < XT - 1 ? 16 * xt + 4 * g + r : (r == 0 ? 16 * xt + g : 16 * XT);
+      float val = 0.f;
+      if (f < D) {
+#pragma unroll
+        for (int k = 0; k < D; ++k)
+          if (f == k) val = corner_bit(corner, D, k) ? gm.rl[1][k] : gm.rl[0][k];
+      } else if (f < D + C)
+        val = a.latent[node * (size_t)C + (size_t)(f - D)];
+      else if (f == D + C)
+        val = 1.f;  // bias column
+      v[r] = val;
+    }
+  }
+  st4(a.X + gid * 4, v);
+  if (xt == 0 && g == 0) a.cw[tile * 16 + j] = w;
+}
+
+template <int D>
+static int launch_gather_nd(const GatherNdArgs& a, hipStream_t stream) {
+  const size_t nthreads = (size_t)a.d.ntiles * XT * 64;
+  STPDE_LAUNCH(k_gather_nd<D>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, stream, a);
+  return stpde_check_launch("k_gather_nd");
+}
+
+// D, P against ntiles, and the 32-bit limits shared by the two entry points
+static int check_nd(const char* who, int D, int P, int ntiles) {
+  if (D != 1 && D != 2 && D != 4) {
+    stpde_set_error("%s: D = %d (1, 2 or 4; dim = 3 has stpde_lig_gather / stpde_lig_reduce_fwd)", who, D);
+    return STPDE_E_BADARG;
+  }
+  const long TP = 16 >> D;
+  if (P < 1 || ntiles < 1 || (long)ntiles * TP < (long)P || (long)ntiles > ((long)P + TP - 1) / TP + 3 ||
+      (long)ntiles * 16 >= (1L << 31)) {
+    stpde_set_error("%s: P = %d points do not fit ntiles = %d row tiles of %ld points (ceil(P / %ld) <= ntiles <= that + 3)", who,
+                    P, ntiles, TP, TP);
+    return STPDE_E_BADARG;
+  }
+  return STPDE_OK;
+}
+
+extern "C" int stpde_lig_gather_nd(const stpde_gather_nd_desc* d, const float* pts, const float* latent, float* X, float* cw,
+                                   void* stream) {
+  if (!d || !pts || !latent || !X || !cw) {
+    stpde_set_error("lig_gather_nd: null pointer");
+    return STPDE_E_BADARG;
+  }
+  int rc = check_nd("lig_gather_nd", d->D, d->P, d->ntiles);
+  if (rc) return rc;
+  if (d->N < 1 || d->B < 1 || d->p_base < 0 || (long)d->p_base + d->P >= (1L << 31)) {
+    stpde_set_error("lig_gather_nd: bad N / B / p_base (p_base + P must fit 31 bits)");
+    return STPDE_E_BADARG;
+  }
+  if (d->C < 1 || d->D + d->C + 1 > 16 * (XT - 1) + 4) {
+    stpde_set_error("lig_gather_nd: D + C + 1 = %d features do not fit the augmented input (<= %d)", d->D + d->C + 1,
+                    16 * (XT - 1) + 4);
+    return STPDE_E_BADARG;
+  }
+  unsigned long long nodes = (unsigned long long)d->B;
+  for (int k = 0; k < d->D; ++k) {
+    if (d->n[k] < 2) {
+      stpde_set_error("lig_gather_nd: grid axis %d has %d nodes (>= 2 per axis)", k, d->n[k]);
+      return STPDE_E_BADARG;
+    }
+    nodes *= (unsigned long long)d->n[k];
+    if (nodes >= (1ull << 31)) {
+      stpde_set_error("lig_gather_nd: latent grid too large for an int32 node index");
+      return STPDE_E_BADARG;
+    }
+  }
+  GatherNdArgs a{*d, pts, latent, X, cw};
+  if (d->D == 1) return launch_gather_nd<1>(a, (hipStream_t)stream);
+  if (d->D == 2) return launch_gather_nd<2>(a, (hipStream_t)stream);
+  return launch_gather_nd<4>(a, (hipStream_t)stream);
+}
+
+struct ReduceNdArgs {
+  int P, n_out;
+  long ldp;
+  const float* src;  // out_pre [ntiles][1][1][256]: lane (g, j) holds output features 4g..4g+3 of row j
+  const float* cw;   // [ntiles][16]
+  float* dst;        // y [n_out][ldp]
+};
+
+// one thread per (point, channel): the 2^D corner terms in corner order, fp32.  A point's rows all lie in its own tile and
+// nothing but its own rows and weights is read, so the result does not depend on how the points were chunked.
+// Addresses: p < P <= ntiles * (16 >> D) (checked on the host), ch < n_out <= 16 -> lane < 64; dst index < n_out * ldp.
+template <int D>
+__global__ __launch_bounds__(256) void k_reduce_nd(ReduceNdArgs a) {
+  constexpr int TP = 16 >> D, NC = 1 << D;
+  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (size_t)a.P * a.n_out) return;
+  const size_t p = gid / a.n_out;
+  const int ch = gid % a.n_out;
+  const size_t tile = p / TP;
+  const int j0 = (int)(p % TP) << D;
+  float y = 0.f;
+#pragma unroll
+  for (int corner = 0; corner < NC; ++corner) {
+    const int j = j0 | corner;
+    const int lane = ((ch >> 2) << 4) | j;
+    y += a.cw[tile * 16 + j] * a.src[tile * 256 + lane * 4 + (ch & 3)];
+  }
+  a.dst[(size_t)ch * a.ldp + p] = y;
+}
+
+template <int D>
+static int launch_reduce_nd(const ReduceNdArgs& a, hipStream_t stream) {
+  const size_t n = (size_t)a.P * a.n_out;
+  STPDE_LAUNCH(k_reduce_nd<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  return stpde_check_launch("k_reduce_nd");
+}
+
+extern "C" int stpde_lig_reduce_nd_fwd(int D, int P, int ntiles, int n_out, const float* out_pre, const float* cw, float* y,
+                                       long ldp, void* stream) {
+  if (!out_pre || !cw || !y) {
+    stpde_set_error("lig_reduce_nd_fwd: null pointer");
+    return STPDE_E_BADARG;
+  }
+  int rc = check_nd("lig_reduce_nd_fwd", D, P, ntiles);
+  if (rc) return rc;
+  if (n_out < 1 || n_out > 16 || ldp < P) {
+    stpde_set_error("lig_reduce_nd_fwd: n_out = %d (1..16) or ldp < P", n_out);
+    return STPDE_E_BADARG;
+  }
+  ReduceNdArgs a{P, n_out, ldp, out_pre, cw, y};
+  if (D == 1) return launch_reduce_nd<1>(a, (hipStream_t)stream);
+  if (D == 2) return launch_reduce_nd<2>(a, (hipStream_t)stream);
+  return launch_reduce_nd<4>(a, (hipStream_t)stream);
 }

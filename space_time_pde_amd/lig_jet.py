@@ -1,4 +1,4 @@
-"""Host driver of the fused LIG + IM-NET jet path (dim = 3) on libstpde_hip.
+"""Host driver of the fused LIG + IM-NET jet path (dim = 3; value-only queries also for dim = 1, 2, 4) on libstpde_hip.
 
 Computes y = query_local_implicit_grid(imnet, latent, pts) together with its first and selected second
 derivatives w.r.t. the query coordinates ("jets") in one forward pass of HIP kernels, and the gradients w.r.t.
@@ -18,12 +18,15 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import XT, GatherDesc, ImNetPlanDesc, JetCfg, LayerDesc, LigWorkspace, XbarDesc, check, ptr, stream_ptr
+from ._lib import XT, GatherDesc, GatherNdDesc, ImNetPlanDesc, JetCfg, LayerDesc, LigWorkspace, XbarDesc, check, ptr, stream_ptr
 
 _FRAG = 256  # floats per 16x16 fragment block
 # widest latent the HIP jet path takes: the augmented input [r(3); latent(c); 1] must fit XT = 3 fragment tiles whose third
 # one is sparse (4 live slots): 3 + c + 1 <= 36.  Wider latents run the generic composed formulation.
 MAX_LATENT_CHANNELS = 16 * (XT - 1) + 4 - 3 - 1
+# the same limit for the value-only path of dim = 1, 2, 4: dim + c + 1 <= MAX_AUG_FEATURES (c <= 34 / 33 / 31)
+MAX_AUG_FEATURES = 16 * (XT - 1) + 4
+ND_VALUE_DIMS = (1, 2, 4)
 
 # Optional per-kernel timing (bench.py): set ``profile`` to a dict; every library call then records a pair of
 # events on the launch stream under its kernel name.  None = no overhead.
@@ -64,13 +67,17 @@ class ImNetPlan:
         return cls._cache[key]
 
     def __init__(self, dim, in_features, out_features, nf):
-        if dim != 3:
-            raise ValueError("the HIP jet path is built for dim=3 query points")
+        # dim = 3: the jet path.  dim = 1, 2, 4: the forward packs serve the value-only path (lig_jets with first=False,
+        # pairs=()) -- the layer kernels index the augmented input by SLOT, and in their one-stream configuration nothing
+        # reads the "tanc" packs (columns 0..2 as coordinate tangents), which mean something for dim = 3 only
+        if dim != 3 and dim not in ND_VALUE_DIMS:
+            raise ValueError("the HIP path is built for dim=3 query points (value-only queries: dim 1, 2, 4)")
         if nf % 16 != 0:
             raise ValueError("the HIP jet path needs nf to be a multiple of 16 (hidden widths are MFMA tiles)")
         self.dz = dim + in_features
-        if self.dz + 1 > 16 * (XT - 1) + 4:
-            raise ValueError("in_features too large for the augmented input of the HIP jet path (max 32 latent channels)")
+        if self.dz + 1 > MAX_AUG_FEATURES:
+            raise ValueError("in_features too large for the augmented input of the HIP path (dim + in_features + 1 <= %d: "
+                             "max 32 latent channels for dim=3)" % MAX_AUG_FEATURES)
         if out_features > 16:
             raise ValueError("out_features > 16 not supported by the HIP jet path")
         self.dim, self.cin, self.cout, self.nf = dim, in_features, out_features, nf
@@ -525,32 +532,57 @@ def _backward_chunk_c(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar=None,
     return None
 
 
+def nd_tiles(P, dim):
+    """Row tiles of P points of a value-only query on a dim-d grid (dim = 1, 2, 4): 16 >> dim points per tile, rounded up to
+    the four tiles of one value-tile pass.  Rows past the last point are padding (zeros, weight 0: stpde_lig_gather_nd)."""
+    tp = 16 >> dim
+    return (-(-P // tp) + 3) // 4 * 4
+
+
+def _gather_nd_desc(meta, latent, Pc, p0, nt):
+    gd = GatherNdDesc()
+    gd.D, gd.P, gd.N, gd.B, gd.C, gd.p_base, gd.ntiles = meta.plan.dim, Pc, meta.N, meta.B, latent.shape[-1], p0, nt
+    for k in range(meta.plan.dim):
+        gd.n[k], gd.lo_c[k], gd.hi_c[k], gd.cube[k] = latent.shape[1 + k], meta.lo_c[k], meta.hi_c[k], meta.cube[k]
+    return gd
+
+
 def _forward_chunk(meta, packs, latent, pts_c, jets, p0, need_grad=True):
     """Run gather + layers 1..5 + reduce for points [p0, p0+Pc) ; returns the buffers backward needs."""
-    if use_pipeline and profile is None:
+    nd = meta.plan.dim != 3       # value-only query on a 1-, 2- or 4-d grid: own gather / corner sum, the same layer kernels
+    if use_pipeline and profile is None and not nd:
         return _forward_chunk_c(meta, packs, latent, pts_c, jets, p0, need_grad)
     plan, cfg, S = meta.plan, meta.cfg, meta.S
     L = _lib.lib()
     st = stream_ptr()
     Pc = pts_c.shape[0]
-    nt = Pc // 2
+    nt = nd_tiles(Pc, plan.dim) if nd else Pc // 2
     dev = pts_c.device
     X = torch.empty(nt * XT * _FRAG, device=dev)
     XR = None           # (round 5: no row-major copy of X; the weight-gradient kernels read X)
     cw = torch.empty(Pc * 8, device=dev) if meta.cfg_out.combo else None
-    coef = torch.empty(Pc * 16, device=dev)
-    cell = torch.empty(Pc, device=dev, dtype=torch.int32)
-    gd = GatherDesc()
-    gd.P, gd.N, gd.B = Pc, meta.N, meta.B
-    gd.n0, gd.n1, gd.n2, gd.C = latent.shape[1], latent.shape[2], latent.shape[3], latent.shape[4]
-    for k in range(3):
-        gd.lo_c[k], gd.hi_c[k], gd.cube[k] = meta.lo_c[k], meta.hi_c[k], meta.cube[k]
-    gd.p_base = p0
-    for k in range(6):
-        gd.alpha[k] = meta.cfg_out.alpha[k]
-    with _timed("gather"):
-        check(L.stpde_lig_gather(C.byref(gd), ptr(pts_c), ptr(latent), ptr(X), ptr(XR), ptr(coef), ptr(cell),
-                                 ptr(cw), st))
+    coef = cell = roww = None
+    if nd:
+        if S != 1 or need_grad:
+            raise NotImplementedError("dim = %d queries run in HIP as value-only forward passes" % plan.dim)
+        roww = torch.empty(nt * 16, device=dev)       # corner weight of every row (cw of stpde_lig_gather_nd)
+        gd = _gather_nd_desc(meta, latent, Pc, p0, nt)
+        with _timed("gather_nd"):
+            check(L.stpde_lig_gather_nd(C.byref(gd), ptr(pts_c), ptr(latent), ptr(X), ptr(roww), st))
+    else:
+        coef = torch.empty(Pc * 16, device=dev)
+        cell = torch.empty(Pc, device=dev, dtype=torch.int32)
+        gd = GatherDesc()
+        gd.P, gd.N, gd.B = Pc, meta.N, meta.B
+        gd.n0, gd.n1, gd.n2, gd.C = latent.shape[1], latent.shape[2], latent.shape[3], latent.shape[4]
+        for k in range(3):
+            gd.lo_c[k], gd.hi_c[k], gd.cube[k] = meta.lo_c[k], meta.hi_c[k], meta.cube[k]
+        gd.p_base = p0
+        for k in range(6):
+            gd.alpha[k] = meta.cfg_out.alpha[k]
+        with _timed("gather"):
+            check(L.stpde_lig_gather(C.byref(gd), ptr(pts_c), ptr(latent), ptr(X), ptr(XR), ptr(coef), ptr(cell),
+                                     ptr(cw), st))
     bufs = [None]
     pv = plan.pack_view
     prev = None
@@ -595,6 +627,11 @@ def _forward_chunk(meta, packs, latent, pts_c, jets, p0, need_grad=True):
                                         ptr(z0) if l == 1 else None, st))
         bufs.append(out)
         prev = out
+    if nd:
+        with _timed("reduce_nd"):
+            check(L.stpde_lig_reduce_nd_fwd(plan.dim, Pc, nt, plan.cout, ptr(bufs[5]), ptr(roww),
+                                            C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2], st))
+        return None
     with _timed("reduce_fwd"):
         check(L.stpde_lig_reduce_fwd(C.byref(meta.cfg_out), S, Pc, plan.cout, ptr(bufs[5]), ptr(coef),
                                      C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2], st))
@@ -818,6 +855,17 @@ def _recompute_chunk(meta, device):
     return max(mult, min(c, DEFAULT_CHUNK))
 
 
+def _nd_chunk_points(meta, dim, device):
+    """Default launch chunk of a value-only query on a dim-d grid (dim = 1, 2, 4), in points: the row tiles of the dim = 3
+    default chunk, cut down (to a power of two) until one chunk's buffers -- X, the five layer buffers, the row weights --
+    take at most half of the call's memory budget / of the free device memory."""
+    tile_bytes = 4 * (sum(_buf_floats(meta, l, 1) for l in range(1, 6)) + XT * _FRAG + 16)
+    tiles = DEFAULT_CHUNK // 2
+    fit = max(4, int(0.5 * _avail_bytes(meta, device) / tile_bytes))
+    tiles = min(tiles, 1 << (fit.bit_length() - 1))
+    return tiles * (16 >> dim)
+
+
 class LigJetFunction(torch.autograd.Function):
     """jets[S, n_out, P] of the LIG+IM-NET composite; differentiable w.r.t. latent grid and IM-NET parameters.
 
@@ -1037,11 +1085,28 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
     precision: "fp32" | "bf16" MFMA operands of the wide layers (None = module setting ``mlp_precision``).
     memory_budget: bytes the stash + backward scratch of this call may take (None = module setting ``memory_budget``, whose
     None means the free device memory); above it the backward recomputes the forward chunk by chunk (``_recompute_chunk``).
+
+    imnet.dim = 1, 2 or 4 (latent_grid [b, n_1..n_d, c], query_pts [b, p, d], d + c + 1 <= 36): VALUE-ONLY queries --
+    first=False, pairs=(), no combo, and nothing that needs a gradient (call it under ``torch.no_grad()`` or with no input /
+    parameter requiring grad); fp32 or fp32x3 operands.  Returns (jets [1, n_out, b*p], []).  Everything else on such grids
+    is the composed formulation of local_implicit_grid.py.
     """
     if not (latent_grid.is_cuda and query_pts.is_cuda):
         raise RuntimeError("the HIP jet path needs CUDA/HIP tensors (no CPU fallback)")
-    if latent_grid.dim() != 5 or query_pts.dim() != 3 or query_pts.shape[-1] != 3:
-        raise ValueError("lig_jets expects latent_grid [b,n0,n1,n2,c] and query_pts [b,p,3]")
+    dim = imnet.dim
+    if dim == 3:
+        if latent_grid.dim() != 5 or query_pts.dim() != 3 or query_pts.shape[-1] != 3:
+            raise ValueError("lig_jets expects latent_grid [b,n0,n1,n2,c] and query_pts [b,p,3]")
+    elif dim in ND_VALUE_DIMS:
+        if latent_grid.dim() != dim + 2 or query_pts.dim() != 3 or query_pts.shape[-1] != dim:
+            raise ValueError("lig_jets expects latent_grid [b,n_1..n_%d,c] and query_pts [b,p,%d]" % (dim, dim))
+        if first or len(pairs) or combo:
+            raise NotImplementedError("dim = %d queries run in HIP as value-only forward passes (no coordinate derivatives)"
+                                      % dim)
+        if min(latent_grid.shape[1:-1]) < 2:
+            raise ValueError("every axis of the latent grid needs at least 2 nodes")
+    else:
+        raise ValueError("lig_jets: dim = %r (3; value-only queries: 1, 2, 4)" % (dim,))
     if latent_grid.dtype != torch.float32 or query_pts.dtype != torch.float32:
         raise ValueError("lig_jets is fp32 only")
     an = activation_name(imnet.activ)
@@ -1063,6 +1128,9 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
     precision = precision or mlp_precision
     if precision not in ("fp32", "bf16", "fp32x3"):
         raise ValueError("mlp precision must be 'fp32', 'bf16' or 'fp32x3'")
+    if dim != 3 and precision == "bf16":
+        # (the value-tile kernels have no one-term bf16 variant; local_implicit_grid routes such a query to the composed ops)
+        raise NotImplementedError("dim = %d value queries run with fp32 or fp32x3 operands" % dim)
     meta.bf16 = precision in ("bf16", "fp32x3")
     meta.nsplit = 3 if precision == "fp32x3" else 1
     meta.packs16 = None
@@ -1086,7 +1154,7 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
         # the tangent row sums: value-only adjoint).  The library serves "all of them" or none.
         meta.packed_mask = 31 if (tail_ok and tan0_rowsum) else 0
     meta.B, meta.N = B, N
-    meta.grid_shape = tuple(latent_grid.shape[1:4])
+    meta.grid_shape = tuple(latent_grid.shape[1:-1])
     meta.lo_c, meta.hi_c, meta.cube = cached_box_constants(meta.grid_shape, xmin, xmax)
     meta.need_wgrad = True
     meta.recompute = force_recompute
@@ -1095,10 +1163,15 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
     P = B * N
     if P == 0:   # empty query set: nothing to launch (the reference returns an empty [b, 0, o] tensor as well)
         return torch.zeros(meta.S_out, plan.cout, 0, device=query_pts.device), ppairs
-    pts = query_pts.detach().reshape(P, 3).contiguous()
+    pts = query_pts.detach().reshape(P, dim).contiguous()
     # tiles hold 2 points; value-only queries are padded to 8 points (4 tiles) for the value-tile kernels
     mult = 8 if meta.S == 1 else 2
-    pad = (-P) % mult
+    if dim != 3:
+        # 16 >> dim points per tile; the gather pads the last tiles of a chunk itself (nd_tiles), the points are not padded.
+        # Default chunk: as many row TILES as the dim = 3 chunk has, so the per-chunk buffers are the same size.
+        mult = 4 * (16 >> dim)
+        chunk_points = chunk_points or _nd_chunk_points(meta, dim, query_pts.device)
+    pad = (-P) % mult if dim == 3 else 0
     if pad:
         pts = torch.cat([pts, pts[-1:].expand(pad, 3)], 0)
     meta.P_pad = P + pad
@@ -1109,6 +1182,9 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
         params += [imnet.fc[k].weight, imnet.fc[k].bias]
     meta.need_grad = torch.is_grad_enabled() and (lat.requires_grad or any(p.requires_grad for p in params)
                                                   or (prm_tensor is not None and prm_tensor.requires_grad))
+    if dim != 3 and meta.need_grad:
+        raise NotImplementedError("dim = %d queries run in HIP as value-only forward passes: call under torch.no_grad() or "
+                                  "without inputs / parameters that require grad" % dim)
     jets = LigJetFunction.apply(meta, lat, pts, prm_tensor, *params)
     if pad:
         jets = jets[:, :, :P]

@@ -5,7 +5,9 @@ is called from inside ``PDELayer.__call__`` (which announces the derivatives its
 ``jet_context``) with an ``ImNet`` decoder on CUDA tensors and 3-d query points, the whole
 gather -> MLP -> corner-weighted sum, INCLUDING the coordinate derivatives, runs in the HIP jet kernels
 (lig_jet.py).  A plain call (no PDE layer) on the same kind of inputs runs the value-only HIP path.
-Other decoders / dimensions use the generic composed formulation.
+Value-only queries on 1-, 2- and 4-d grids (no jet request, nothing that needs a gradient) run in HIP as well: a gather and
+a corner sum of their own around the same IM-NET layer kernels (``_nd_value_eligible``).
+Other decoders / dimensions / requests use the generic composed formulation.
 """
 import threading
 
@@ -54,6 +56,34 @@ def _fast_eligible(model, latent_grid, query_pts):
             and model.nf % 16 == 0 and model.out_features <= 16 and model.in_features <= lig_jet.MAX_LATENT_CHANNELS
             and latent_grid.shape[-1] == model.in_features
             and lig_jet.activation_name(model.activ) is not None)
+
+
+def _nd_value_eligible(model, latent_grid, query_pts, req=None):
+    """A value-only query on a 1-, 2- or 4-d grid that the HIP path serves: ImNet decoder, CUDA fp32, nf a multiple of 16,
+    out_features <= 16, the augmented input [r(d); latent(c); 1] within the 36 slots of the layer kernels' input image
+    (c <= 34 / 33 / 31 for d = 1 / 2 / 4 -- the reference's own 4-d test case, c = 32, is one channel too wide and stays on
+    the composed formulation), every grid axis >= 2 nodes, fp32 or fp32x3 operands, no jet request for these points and
+    nothing that needs a gradient (no_grad, or no input / parameter requiring grad).  Jets, training backward and point
+    gradients on such grids keep the composed formulation."""
+    if not isinstance(model, ImNet) or model.dim not in lig_jet.ND_VALUE_DIMS:
+        return False
+    d = model.dim
+    if not (latent_grid.dim() == d + 2 and query_pts.dim() == 3 and query_pts.shape[-1] == d
+            and latent_grid.is_cuda and query_pts.is_cuda
+            and latent_grid.dtype == torch.float32 and query_pts.dtype == torch.float32
+            and model.nf % 16 == 0 and model.out_features <= 16
+            and d + model.in_features + 1 <= lig_jet.MAX_AUG_FEATURES
+            and latent_grid.shape[-1] == model.in_features and latent_grid.shape[0] == query_pts.shape[0]
+            and min(latent_grid.shape[1:-1]) >= 2
+            and lig_jet.mlp_precision in ("fp32", "fp32x3")
+            and lig_jet.activation_name(model.activ) is not None):
+        return False
+    if req is not None and req.x is query_pts:
+        return False
+    if torch.is_grad_enabled() and (query_pts.requires_grad or latent_grid.requires_grad
+                                    or any(p.requires_grad for p in model.parameters())):
+        return False
+    return True
 
 
 def _xmin_is_zero(xmin, xmax=None, shape3=None):
@@ -140,6 +170,11 @@ def query_local_implicit_grid(model, latent_grid, query_pts, xmin, xmax):
             jets, _ = lig_jet.lig_jets(model, latent_grid, query_pts, xmin, xmax, False, ())
             stats["hip_value_calls"] += 1
             return jets[0].t().reshape(query_pts.shape[0], query_pts.shape[1], jets.shape[1])
+    if _nd_value_eligible(model, latent_grid, query_pts, req) \
+            and _xmin_is_zero(xmin, xmax, tuple(latent_grid.shape[1:-1])):
+        jets, _ = lig_jet.lig_jets(model, latent_grid, query_pts, xmin, xmax, False, ())
+        stats["hip_value_calls"] += 1
+        return jets[0].t().reshape(query_pts.shape[0], query_pts.shape[1], jets.shape[1])
     stats["generic_calls"] += 1
     corner_values, weights, x_relative = rgi._coefficients_autograd(latent_grid, query_pts, xmin, xmax) \
         if (query_pts.requires_grad and torch.is_grad_enabled()) else \

@@ -403,8 +403,8 @@ int stpde_interp_bwd_grid(const stpde_interp_desc* d, const float* pts, const fl
  * ceil(P / (16 >> D)) by up to 3 (the value-tile mode wants a multiple of 4): rows of points >= P are written as zeros
  * with weight 0 and belong to no output point; nothing is read or written past P points or ntiles tiles.  The cell index
  * is clamped to [0, n_k - 2] after the float clip and the batch index to B - 1, so no coordinate value -- NaN, infinite,
- * outside the box -- forms an address outside the latent grid.  No derivative streams and no backward: such requests take
- * the composed formulation (local_implicit_grid.py).  Refused with STPDE_E_BADARG: D other than 1, 2, 4; P < 1; ntiles
+ * outside the box -- forms an address outside the latent grid.  No derivative streams (such requests take the composed
+ * formulation, local_implicit_grid.py); the training backward of the value stream is the next block.  Refused with STPDE_E_BADARG: D other than 1, 2, 4; P < 1; ntiles
  * outside [ceil(P / (16 >> D)), that + 3]; an axis with fewer than 2 nodes; D + C + 1 > 36; B * prod(n) or p_base + P
  * beyond 31 bits; n_out outside 1..16; ldp < P; a null pointer. */
 typedef struct {
@@ -418,6 +418,35 @@ int stpde_lig_gather_nd(const stpde_gather_nd_desc* d, const float* pts, const f
                         float* cw /* [ntiles][16] */, void* stream);
 int stpde_lig_reduce_nd_fwd(int D, int P, int ntiles, int n_out, const float* out_pre /* fc5 rows [ntiles][64][4] */,
                             const float* cw, float* y, long ldp, void* stream);
+
+/* ---- training backward on the same grids (dim = 1, 2, 4; value stream only) -----------------------------------------
+ * Between these three calls run, unchanged and in their S1 = S2 = 0 configuration over ntiles row tiles, stpde_jet_layer_fwd
+ * with the z0 stash / stpde_jet_tail_fwd_p (forward), stpde_jet_wgrad, stpde_jet_layer_bwd / _bwd_to, stpde_jet_tail_bwd_p,
+ * stpde_lig_xbar_rows and stpde_lig_cell_sort (backward).  Row numbering is the gather's: tile * 16 + j = point * 2^D + corner.
+ *   stpde_lig_reduce_nd_bwd      adjoint of stpde_lig_reduce_nd_fwd: lane (g, j), register r of tile t of abar_out receives
+ *                                cw[16 t + j] * y_bar[(4 g + r) * ldp + p], p = t * (16 >> D) + (j >> D); zeros where p >= P
+ *                                or 4 g + r >= n_out.  EVERY float of the ntiles blocks is written (the buffer held the
+ *                                forward's fc5 rows); nothing is read for p >= P.  Checks of stpde_lig_reduce_nd_fwd.
+ *   stpde_lig_cell_nd            cell[p] = linear index, batch included, of the corner-0 node of the cell of point p: the
+ *                                same clip, cell index and batch clamp as stpde_lig_gather_nd (so < B * prod(n) for every
+ *                                coordinate value); the counterpart of the `cell` output of stpde_lig_gather.  Checks of
+ *                                stpde_lig_gather_nd.
+ *   stpde_lig_dlatent_reduce_nd  stpde_lig_dlatent_reduce for 2^D corners: dlatent[node] += sum over corners 0 .. 2^D - 1
+ *                                (first axis most significant; a corner whose owning cell lies outside [0, n_k - 2] on any
+ *                                axis is skipped) and the points of the owning cell in ascending perm position of
+ *                                xrows[perm[q] * 2^D + corner], fp32, fixed order: bit-reproducible.  n = HOST array of the D
+ *                                axis lengths.  xrows is what stpde_lig_xbar_rows wrote for the chunk, [16 * ntiles][CP]
+ *                                floats (padding rows of the last tiles included; CP = C rounded up to a multiple of 4); perm
+ *                                [P] / start [n_nodes + 1] from stpde_lig_cell_sort on the output of stpde_lig_cell_nd.
+ *                                Refused: D other than 1, 2, 4; an axis with fewer than 2 nodes; C outside 1..64; B < 1;
+ *                                B * prod(n) beyond 31 bits; a null pointer.
+ * stpde_lig_xbar_rows serves C <= 32, so training on these grids needs in_features <= 32.  There is no atomic variant of the
+ * d-latent sum on these grids. */
+int stpde_lig_reduce_nd_bwd(int D, int P, int ntiles, int n_out, const float* y_bar, long ldp, const float* cw,
+                            float* abar_out /* [ntiles][64][4] */, void* stream);
+int stpde_lig_cell_nd(const stpde_gather_nd_desc* d, const float* pts, int* cell /* [P] */, void* stream);
+int stpde_lig_dlatent_reduce_nd(int D, int B, const int* n /* [D] on the host */, int C, const float* xrows, const int* perm,
+                                const int* start, float* dlatent, void* stream);
 
 /* ---- a10: 3-D convolution of the U-Net encoder (src/unet3d.py:39-56: nn.Conv3d 1x1x1 and 3x3x3/pad 1, stride 1)
  * Activations are channels-last: x [B][T][Z][X][Ci], y [B][T][Z][X][Co], Ci and Co multiples of 16.

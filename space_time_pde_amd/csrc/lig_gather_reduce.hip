@@ -7,7 +7,9 @@
 //   k_reduce_bwd  its adjoint
 //   k_xbar        d latent: xbar = sum_l W_s,l^T abar_l, scatter-added at the 8 corner nodes (backward of the
 //                 advanced-index gather at src/regular_nd_grid_interpolation.py:65-66)
-//   k_gather_nd / k_reduce_nd   the value-only gather and corner sum for dim = 1, 2, 4 (end of this file)
+//   k_gather_nd / k_reduce_nd   the gather and corner sum for dim = 1, 2, 4 (end of this file)
+//   k_reduce_nd_bwd / k_cell_nd / k_dlat_reduce_nd   what the training backward on such grids adds to the dim-agnostic layer,
+//                 weight-gradient and k_xbar kernels: adjoint of the corner sum, cell id per point, per-node d-latent sum
 // All of these are HBM/L2-bound byte movers; no MFMA except the small xbar GEMM.
 #include "interp_geom.h"
 
@@ -835,35 +837,42 @@ static int check_nd(const char* who, int D, int P, int ntiles) {
   return STPDE_OK;
 }
 
-extern "C" int stpde_lig_gather_nd(const stpde_gather_nd_desc* d, const float* pts, const float* latent, float* X, float* cw,
-                                   void* stream) {
-  if (!d || !pts || !latent || !X || !cw) {
-    stpde_set_error("lig_gather_nd: null pointer");
-    return STPDE_E_BADARG;
-  }
-  int rc = check_nd("lig_gather_nd", d->D, d->P, d->ntiles);
+// the descriptor checks shared by stpde_lig_gather_nd and stpde_lig_cell_nd (which must name exactly the cell the gather read)
+static int check_gather_nd_desc(const char* who, const stpde_gather_nd_desc* d) {
+  int rc = check_nd(who, d->D, d->P, d->ntiles);
   if (rc) return rc;
   if (d->N < 1 || d->B < 1 || d->p_base < 0 || (long)d->p_base + d->P >= (1L << 31)) {
-    stpde_set_error("lig_gather_nd: bad N / B / p_base (p_base + P must fit 31 bits)");
+    stpde_set_error("%s: bad N / B / p_base (p_base + P must fit 31 bits)", who);
     return STPDE_E_BADARG;
   }
   if (d->C < 1 || d->D + d->C + 1 > 16 * (XT - 1) + 4) {
-    stpde_set_error("lig_gather_nd: D + C + 1 = %d features do not fit the augmented input (<= %d)", d->D + d->C + 1,
+    stpde_set_error("%s: D + C + 1 = %d features do not fit the augmented input (<= %d)", who, d->D + d->C + 1,
                     16 * (XT - 1) + 4);
     return STPDE_E_BADARG;
   }
   unsigned long long nodes = (unsigned long long)d->B;
   for (int k = 0; k < d->D; ++k) {
     if (d->n[k] < 2) {
-      stpde_set_error("lig_gather_nd: grid axis %d has %d nodes (>= 2 per axis)", k, d->n[k]);
+      stpde_set_error("%s: grid axis %d has %d nodes (>= 2 per axis)", who, k, d->n[k]);
       return STPDE_E_BADARG;
     }
     nodes *= (unsigned long long)d->n[k];
     if (nodes >= (1ull << 31)) {
-      stpde_set_error("lig_gather_nd: latent grid too large for an int32 node index");
+      stpde_set_error("%s: latent grid too large for an int32 node index", who);
       return STPDE_E_BADARG;
     }
   }
+  return STPDE_OK;
+}
+
+extern "C" int stpde_lig_gather_nd(const stpde_gather_nd_desc* d, const float* pts, const float* latent, float* X, float* cw,
+                                   void* stream) {
+  if (!d || !pts || !latent || !X || !cw) {
+    stpde_set_error("lig_gather_nd: null pointer");
+    return STPDE_E_BADARG;
+  }
+  int rc = check_gather_nd_desc("lig_gather_nd", d);
+  if (rc) return rc;
   GatherNdArgs a{*d, pts, latent, X, cw};
   if (d->D == 1) return launch_gather_nd<1>(a, (hipStream_t)stream);
   if (d->D == 2) return launch_gather_nd<2>(a, (hipStream_t)stream);
@@ -923,4 +932,225 @@ extern "C" int stpde_lig_reduce_nd_fwd(int D, int P, int ntiles, int n_out, cons
   if (D == 1) return launch_reduce_nd<1>(a, (hipStream_t)stream);
   if (D == 2) return launch_reduce_nd<2>(a, (hipStream_t)stream);
   return launch_reduce_nd<4>(a, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// training backward on 1-, 2- and 4-d grids: the three kernels around the dimension-agnostic S = (0, 0) layer / weight-gradient
+// kernels and k_xbar (rows variant).  Row numbering is the gather's: row tile * 16 + j = point * 2^D + corner.
+//
+// Addresses.  Every grid below is derived from ntiles, P or the node count alone, and every index is bounded for EVERY
+// input value (NaN, infinite, out-of-box coordinates included):
+//   k_reduce_nd_bwd   abar_out  gid < ntiles * 64, one float4 per thread: all of [ntiles][64][4] is written (zeros for
+//                               padding rows and features >= n_out -- the buffer held the forward's fc5 rows and the layer
+//                               kernels read all of it)
+//                     cw        tile * 16 + j < ntiles * 16, read only where p < P
+//                     y_bar     (4g + r) * ldp + p with 4g + r < n_out, p < P <= ldp; nothing is read for p >= P
+//   k_cell_nd         pts       p < P, k < D;  cell[p], p < P.  Value: batch clamped to B - 1, cell index clamped to
+//                               [0, n_k - 2] by geom_axis() -> cell < B * prod(n) < 2^31 (checked on the host)
+//   k_dlat_reduce_nd  start     cell and cell + 1 with cell < n_nodes: start has n_nodes + 1 entries
+//                     perm      q in [start[cell], start[cell + 1]) within [0, P) (stpde_lig_cell_sort: start[n_nodes] = P)
+//                     xrows     row = perm[q] * 2^D + corner < P * 2^D <= 16 * ntiles: inside the [16 * ntiles][CP] rows k_xbar
+//                               wrote (the buffer of a chunk is 16 * ntiles * CP floats, padding rows of the last tiles included)
+//                     dlatent   node < n_nodes, channel 4 c4 + r < C
+// ---------------------------------------------------------------------------------------------------------
+struct ReduceNdBwdArgs {
+  int P, ntiles, n_out;
+  long ldp;
+  const float* ybar;  // [n_out][ldp]
+  const float* cw;    // [ntiles][16]
+  float* dst;         // abar_out [ntiles][64][4]
+};
+
+// adjoint of k_reduce_nd: one thread per (row tile, lane), one 16-byte store
+template <int D>
+__global__ __launch_bounds__(256) void k_reduce_nd_bwd(ReduceNdBwdArgs a) {
+  constexpr int TP = 16 >> D;
+  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (size_t)a.ntiles * 64) return;
+  const int lane = gid & 63;
+  const size_t tile = gid >> 6;
+  const int g = lane >> 4, j = lane & 15;
+  const size_t p = tile * TP + (j >> D);
+  f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (p < (size_t)a.P && 4 * g < a.n_out) {
+    const float w = a.cw[tile * 16 + j];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (4 * g + r < a.n_out) v[r] = w * a.ybar[(size_t)(4 * g + r) * a.ldp + p];
+  }
+  st4(a.dst + gid * 4, v);
+}
+
+template <int D>
+static int launch_reduce_nd_bwd(const ReduceNdBwdArgs& a, hipStream_t stream) {
+  const size_t n = (size_t)a.ntiles * 64;
+  STPDE_LAUNCH(k_reduce_nd_bwd<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  return stpde_check_launch("k_reduce_nd_bwd");
+}
+
+extern "C" int stpde_lig_reduce_nd_bwd(int D, int P, int ntiles, int n_out, const float* y_bar, long ldp, const float* cw,
+                                       float* abar_out, void* stream) {
+  if (!y_bar || !cw || !abar_out) {
+    stpde_set_error("lig_reduce_nd_bwd: null pointer");
+    return STPDE_E_BADARG;
+  }
+  int rc = check_nd("lig_reduce_nd_bwd", D, P, ntiles);
+  if (rc) return rc;
+  if (n_out < 1 || n_out > 16 || ldp < P) {
+    stpde_set_error("lig_reduce_nd_bwd: n_out = %d (1..16) or ldp < P", n_out);
+    return STPDE_E_BADARG;
+  }
+  ReduceNdBwdArgs a{P, ntiles, n_out, ldp, y_bar, cw, abar_out};
+  if (D == 1) return launch_reduce_nd_bwd<1>(a, (hipStream_t)stream);
+  if (D == 2) return launch_reduce_nd_bwd<2>(a, (hipStream_t)stream);
+  return launch_reduce_nd_bwd<4>(a, (hipStream_t)stream);
+}
+
+struct CellNdArgs {
+  stpde_gather_nd_desc d;
+  const float* pts;
+  int* cell;
+};
+
+// one thread per point: the same geom_axis() calls and the same batch clamp as k_gather_nd, so cell[p] names exactly the cell
+// whose corners the gather read
+template <int D>
+__global__ __launch_bounds__(256) void k_cell_nd(CellNdArgs a) {
+  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= (size_t)a.d.P) return;
+  GeomN gm;
+#pragma unroll
+  for (int k = 0; k < D; ++k) geom_axis(gm, k, a.pts[p * D + k], a.d.lo_c[k], a.d.hi_c[k], a.d.cube[k], a.d.n[k]);
+  size_t b = ((size_t)a.d.p_base + p) / (size_t)a.d.N;
+  b = b > (size_t)(a.d.B - 1) ? (size_t)(a.d.B - 1) : b;
+  size_t node = b;
+#pragma unroll
+  for (int k = 0; k < D; ++k) node = node * (size_t)a.d.n[k] + (size_t)gm.i0[k];
+  a.cell[p] = (int)node;
+}
+
+template <int D>
+static int launch_cell_nd(const CellNdArgs& a, hipStream_t stream) {
+  STPDE_LAUNCH(k_cell_nd<D>, dim3((unsigned)(((size_t)a.d.P + 255) / 256)), dim3(256), 0, stream, a);
+  return stpde_check_launch("k_cell_nd");
+}
+
+extern "C" int stpde_lig_cell_nd(const stpde_gather_nd_desc* d, const float* pts, int* cell, void* stream) {
+  if (!d || !pts || !cell) {
+    stpde_set_error("lig_cell_nd: null pointer");
+    return STPDE_E_BADARG;
+  }
+  int rc = check_gather_nd_desc("lig_cell_nd", d);
+  if (rc) return rc;
+  CellNdArgs a{*d, pts, cell};
+  if (d->D == 1) return launch_cell_nd<1>(a, (hipStream_t)stream);
+  if (d->D == 2) return launch_cell_nd<2>(a, (hipStream_t)stream);
+  return launch_cell_nd<4>(a, (hipStream_t)stream);
+}
+
+struct DlatNdArgs {
+  int n[4];
+  int C, CP;
+  size_t nnodes;        // B * prod(n)
+  const float* xrows;   // [16 * ntiles][CP]   row = 2^D * point + corner
+  const int* perm;
+  const int* start;
+  float* dlatent;       // [B][n_0..n_{D-1}][C], accumulated into (+=)
+};
+
+// k_dlat_reduce for 2^D corners: one group of 16 lanes per node (lane = float4 of channels); corners 0 .. 2^D - 1 in the order
+// of interp_nd.hip (first axis most significant), the points of the owning cell in ascending perm position, fp32
+template <int D>
+__global__ __launch_bounds__(256) void k_dlat_reduce_nd(DlatNdArgs a) {
+  constexpr int NC = 1 << D;
+  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int c4 = gid & 15;
+  const size_t node = gid >> 4;
+  if (node >= a.nnodes || 4 * c4 >= a.CP) return;
+  int idx[D];
+  size_t stride[D];
+  {
+    size_t rest = node, s = 1;
+#pragma unroll
+    for (int k = D - 1; k >= 0; --k) {
+      idx[k] = (int)(rest % (size_t)a.n[k]);
+      rest /= (size_t)a.n[k];
+      stride[k] = s;
+      s *= (size_t)a.n[k];
+    }
+  }
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  bool any = false;
+#pragma unroll
+  for (int corner = 0; corner < NC; ++corner) {
+    bool inside = true;
+    size_t off = 0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const int bit = corner_bit(corner, D, k);
+      const int c = idx[k] - bit;                      // the cell for which this node is corner `corner`
+      inside = inside && c >= 0 && c <= a.n[k] - 2;
+      off += (size_t)bit * stride[k];
+    }
+    if (!inside) continue;                             // (off <= node then: every bit set has idx[k] >= 1)
+    const size_t cell = node - off;
+    const int q0 = a.start[cell], q1 = a.start[cell + 1];
+    for (int q = q0; q < q1; ++q) {
+      const size_t row = (size_t)a.perm[q] * NC + corner;
+      acc += ld4(a.xrows + row * a.CP + 4 * c4);
+      any = true;
+    }
+  }
+  if (!any) return;
+  float* dst = a.dlatent + node * a.C + 4 * c4;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (4 * c4 + r < a.C) dst[r] += acc[r];
+}
+
+template <int D>
+static int launch_dlat_reduce_nd(const DlatNdArgs& a, hipStream_t stream) {
+  const size_t n = a.nnodes * 16;
+  STPDE_LAUNCH(k_dlat_reduce_nd<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  return stpde_check_launch("k_dlat_reduce_nd");
+}
+
+extern "C" int stpde_lig_dlatent_reduce_nd(int D, int B, const int* n, int C, const float* xrows, const int* perm,
+                                           const int* start, float* dlatent, void* stream) {
+  if (!n || !xrows || !perm || !start || !dlatent) {
+    stpde_set_error("lig_dlatent_reduce_nd: null pointer");
+    return STPDE_E_BADARG;
+  }
+  if (D != 1 && D != 2 && D != 4) {
+    stpde_set_error("lig_dlatent_reduce_nd: D = %d (1, 2 or 4; dim = 3 has stpde_lig_dlatent_reduce)", D);
+    return STPDE_E_BADARG;
+  }
+  if (B < 1 || C < 1 || C > 64) {
+    stpde_set_error("lig_dlatent_reduce_nd: bad B or C = %d (1..64)", C);
+    return STPDE_E_BADARG;
+  }
+  DlatNdArgs a{};
+  unsigned long long nodes = (unsigned long long)B;
+  for (int k = 0; k < D; ++k) {
+    if (n[k] < 2) {
+      stpde_set_error("lig_dlatent_reduce_nd: grid axis %d has %d nodes (>= 2 per axis)", k, n[k]);
+      return STPDE_E_BADARG;
+    }
+    nodes *= (unsigned long long)n[k];
+    if (nodes >= (1ull << 31)) {
+      stpde_set_error("lig_dlatent_reduce_nd: latent grid too large for an int32 node index");
+      return STPDE_E_BADARG;
+    }
+    a.n[k] = n[k];
+  }
+  a.C = C;
+  a.CP = (C + 3) / 4 * 4;
+  a.nnodes = (size_t)nodes;
+  a.xrows = xrows;
+  a.perm = perm;
+  a.start = start;
+  a.dlatent = dlatent;
+  if (D == 1) return launch_dlat_reduce_nd<1>(a, (hipStream_t)stream);
+  if (D == 2) return launch_dlat_reduce_nd<2>(a, (hipStream_t)stream);
+  return launch_dlat_reduce_nd<4>(a, (hipStream_t)stream);
 }

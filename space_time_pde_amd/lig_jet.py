@@ -1,4 +1,5 @@
-"""Host driver of the fused LIG + IM-NET jet path (dim = 3; value-only queries also for dim = 1, 2, 4) on libstpde_hip.
+"""Host driver of the fused LIG + IM-NET jet path (dim = 3; value queries, and opt-in their training backward, also for
+dim = 1, 2, 4) on libstpde_hip.
 
 Computes y = query_local_implicit_grid(imnet, latent, pts) together with its first and selected second
 derivatives w.r.t. the query coordinates ("jets") in one forward pass of HIP kernels, and the gradients w.r.t.
@@ -27,6 +28,20 @@ MAX_LATENT_CHANNELS = 16 * (XT - 1) + 4 - 3 - 1
 # the same limit for the value-only path of dim = 1, 2, 4: dim + c + 1 <= MAX_AUG_FEATURES (c <= 34 / 33 / 31)
 MAX_AUG_FEATURES = 16 * (XT - 1) + 4
 ND_VALUE_DIMS = (1, 2, 4)
+# widest latent the training backward on such grids takes: k_xbar<XL> (the latent adjoint) exists for XL = 1, 2
+ND_TRAIN_MAX_CHANNELS = 32
+
+# Opt-in: train through value queries on 1-, 2- and 4-d grids in HIP (gradients w.r.t. the latent grid and the IM-NET
+# parameters; ``set_nd_backward`` / STPDE_ND_BACKWARD=1, read once here).  Off, a query on such a grid that needs a gradient
+# takes the composed formulation (local_implicit_grid.py) and lig_jets refuses it.
+nd_backward = os.getenv("STPDE_ND_BACKWARD", "0").strip().lower() not in ("", "0", "false", "no", "off")
+
+
+def set_nd_backward(on):
+    """Switch the HIP training backward of dim = 1, 2, 4 value queries on or off; returns the previous setting."""
+    global nd_backward
+    prev, nd_backward = nd_backward, bool(on)
+    return prev
 
 # Optional per-kernel timing (bench.py): set ``profile`` to a dict; every library call then records a pair of
 # events on the launch stream under its kernel name.  None = no overhead.
@@ -67,9 +82,11 @@ class ImNetPlan:
         return cls._cache[key]
 
     def __init__(self, dim, in_features, out_features, nf):
-        # dim = 3: the jet path.  dim = 1, 2, 4: the forward packs serve the value-only path (lig_jets with first=False,
-        # pairs=()) -- the layer kernels index the augmented input by SLOT, and in their one-stream configuration nothing
-        # reads the "tanc" packs (columns 0..2 as coordinate tangents), which mean something for dim = 3 only
+        # dim = 3: the jet path.  dim = 1, 2, 4: the packs serve the value path (lig_jets with first=False, pairs=()) and its
+        # training backward -- the layer kernels index the augmented input by SLOT ("Ws", the latent columns "WsL" of the
+        # d-latent GEMM and the unpack map of the weight gradients all go through the slot map), and in their one-stream
+        # configuration nothing reads the "tanc" packs (columns 0..2 as coordinate tangents), which mean something for
+        # dim = 3 only
         if dim != 3 and dim not in ND_VALUE_DIMS:
             raise ValueError("the HIP path is built for dim=3 query points (value-only queries: dim 1, 2, 4)")
         if nf % 16 != 0:
@@ -533,7 +550,7 @@ def _backward_chunk_c(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar=None,
 
 
 def nd_tiles(P, dim):
-    """Row tiles of P points of a value-only query on a dim-d grid (dim = 1, 2, 4): 16 >> dim points per tile, rounded up to
+    """Row tiles of P points of a value query on a dim-d grid (dim = 1, 2, 4): 16 >> dim points per tile, rounded up to
     the four tiles of one value-tile pass.  Rows past the last point are padding (zeros, weight 0: stpde_lig_gather_nd)."""
     tp = 16 >> dim
     return (-(-P // tp) + 3) // 4 * 4
@@ -549,7 +566,7 @@ def _gather_nd_desc(meta, latent, Pc, p0, nt):
 
 def _forward_chunk(meta, packs, latent, pts_c, jets, p0, need_grad=True):
     """Run gather + layers 1..5 + reduce for points [p0, p0+Pc) ; returns the buffers backward needs."""
-    nd = meta.plan.dim != 3       # value-only query on a 1-, 2- or 4-d grid: own gather / corner sum, the same layer kernels
+    nd = meta.plan.dim != 3       # value query on a 1-, 2- or 4-d grid: own gather / corner sum, the same layer kernels
     if use_pipeline and profile is None and not nd:
         return _forward_chunk_c(meta, packs, latent, pts_c, jets, p0, need_grad)
     plan, cfg, S = meta.plan, meta.cfg, meta.S
@@ -563,7 +580,7 @@ def _forward_chunk(meta, packs, latent, pts_c, jets, p0, need_grad=True):
     cw = torch.empty(Pc * 8, device=dev) if meta.cfg_out.combo else None
     coef = cell = roww = None
     if nd:
-        if S != 1 or need_grad:
+        if S != 1 or (need_grad and not nd_backward):
             raise NotImplementedError("dim = %d queries run in HIP as value-only forward passes" % plan.dim)
         roww = torch.empty(nt * 16, device=dev)       # corner weight of every row (cw of stpde_lig_gather_nd)
         gd = _gather_nd_desc(meta, latent, Pc, p0, nt)
@@ -631,7 +648,11 @@ def _forward_chunk(meta, packs, latent, pts_c, jets, p0, need_grad=True):
         with _timed("reduce_nd"):
             check(L.stpde_lig_reduce_nd_fwd(plan.dim, Pc, nt, plan.cout, ptr(bufs[5]), ptr(roww),
                                             C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2], st))
-        return None
+        if not need_grad:
+            return None
+        # training (``nd_backward``): the S = 1 layer configuration above kept z0; the backward needs the points again for
+        # the cell ids (stpde_lig_cell_nd) and the row weights for the adjoint of the corner sum
+        return dict(X=X, bufs=bufs, z0=z0, roww=roww, pts_c=pts_c, p0=p0, Pc=Pc, nt=nt)
     with _timed("reduce_fwd"):
         check(L.stpde_lig_reduce_fwd(C.byref(meta.cfg_out), S, Pc, plan.cout, ptr(bufs[5]), ptr(coef),
                                      C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2], st))
@@ -640,23 +661,33 @@ def _forward_chunk(meta, packs, latent, pts_c, jets, p0, need_grad=True):
 
 def _backward_chunk(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar=None, after_dlatent=None):
     """reduce_bwd -> for l = 5..1: wgrad_l (reads abar_l and the still intact pre-activations of layer l-1), then
-    dgrad_l (overwrites them with abar_{l-1}) -> wgrad_0 -> xbar/scatter."""
+    dgrad_l (overwrites them with abar_{l-1}) -> wgrad_0 -> xbar/scatter.
+
+    dim = 1, 2, 4 (``nd_backward``): stpde_lig_reduce_nd_bwd, the same S = 1 wgrad / dgrad sequence over the chunk's
+    ``nd_tiles`` row tiles, then xbar_rows -> cell_nd -> cell_sort -> dlatent_reduce_nd.  d latent on these grids is ALWAYS
+    the deterministic per-node sum: ``deterministic_dlatent = False`` is ignored, there is no atomic variant."""
     if "ws" in saved:
         return _backward_chunk_c(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar, after_dlatent)
     plan, cfg, S = meta.plan, meta.cfg, meta.S
     L = _lib.lib()
     st = stream_ptr()
     Pc, p0 = saved["Pc"], saved["p0"]
-    nt = Pc // 2
-    X, XR, coef, cell, bufs = saved["X"], saved["XR"], saved["coef"], saved["cell"], saved["bufs"]
-    cw = saved["cw"]
+    nd = plan.dim != 3
+    nt = saved["nt"] if nd else Pc // 2
+    X, bufs = saved["X"], saved["bufs"]
+    XR, coef, cell, cw = (X, None, None, None) if nd else (saved[k] for k in ("XR", "coef", "cell", "cw"))
     dev = X.device
     pv = plan.pack_view
     SP0 = 1 + cfg.S1
     # adjoint of the fc5 output rows (overwrites the forward's out_pre buffer)
-    with _timed("reduce_bwd"):
-        check(L.stpde_lig_reduce_bwd(C.byref(meta.cfg_out), S, Pc, plan.cout, C.c_void_p(jets_bar.data_ptr() + 4 * p0),
-                                     jets_bar.shape[2], ptr(coef), ptr(bufs[5]), st))
+    if nd:
+        with _timed("reduce_nd_bwd"):
+            check(L.stpde_lig_reduce_nd_bwd(plan.dim, Pc, nt, plan.cout, C.c_void_p(jets_bar.data_ptr() + 4 * p0),
+                                            jets_bar.shape[2], ptr(saved["roww"]), ptr(bufs[5]), st))
+    else:
+        with _timed("reduce_bwd"):
+            check(L.stpde_lig_reduce_bwd(C.byref(meta.cfg_out), S, Pc, plan.cout, C.c_void_p(jets_bar.data_ptr() + 4 * p0),
+                                         jets_bar.shape[2], ptr(coef), ptr(bufs[5]), st))
     # layer-0 adjoint: the value stream as fragment blocks; the three tangent streams only as per-tile row sums (their
     # layer-0 "input" is the constant column W0[:, d], so only sum_rows matters): 32 + 6 KB per tile instead of 128 KB
     MT0 = plan.layers[0]["MT"]
@@ -738,7 +769,7 @@ def _backward_chunk(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar=None, a
     if dlatent is not None:
         xd = XbarDesc()
         xd.ntiles, xd.nlayers, xd.C = nt, 5, plan.cin
-        xd.n1, xd.n2 = meta.grid_shape[1], meta.grid_shape[2]
+        xd.n1, xd.n2 = (1, 1) if nd else meta.grid_shape[1:3]      # (read by the atomic scatter only)
         ab = (C.c_void_p * 5)()
         wt = (C.c_void_p * 5)()
         for l in range(5):
@@ -747,7 +778,25 @@ def _backward_chunk(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar=None, a
             xd.packed[l], xd.S[l] = (meta.packed_mask >> l) & 1, (S if l else 1)
             ab[l] = (abar0 if l == 0 else abar[l]).data_ptr()
             wt[l] = pv(packs, l, "WsL").data_ptr()
-        if not deterministic_dlatent:
+        if nd:
+            # per-row adjoints for all 16 * nt rows (k_xbar writes the padding rows of the last tiles too), the cell id of
+            # every point, then the per-node sum over 2^dim corners in fixed order
+            cp = (plan.cin + 3) // 4 * 4
+            xrows = torch.empty(16 * nt * cp, device=dev)
+            n_nodes = meta.B * int(np.prod(meta.grid_shape))
+            cell = torch.empty(Pc, device=dev, dtype=torch.int32)
+            perm = torch.empty(Pc, device=dev, dtype=torch.int32)
+            start = torch.empty(n_nodes + 1, device=dev, dtype=torch.int32)
+            nb = int(L.stpde_lig_sort_tmp_bytes(Pc, n_nodes))
+            tmp = torch.empty(nb, device=dev, dtype=torch.uint8)
+            gd = _gather_nd_desc(meta, dlatent, Pc, p0, nt)
+            with _timed("xbar_scatter"):
+                check(L.stpde_lig_xbar_rows(C.byref(xd), ab, wt, ptr(xrows), st))
+                check(L.stpde_lig_cell_nd(C.byref(gd), ptr(saved["pts_c"]), ptr(cell), st))
+                check(L.stpde_lig_cell_sort(Pc, n_nodes, ptr(cell), ptr(perm), ptr(start), ptr(tmp), nb, st))
+                check(L.stpde_lig_dlatent_reduce_nd(plan.dim, meta.B, (C.c_int * 4)(*meta.grid_shape), plan.cin, ptr(xrows),
+                                                    ptr(perm), ptr(start), ptr(dlatent), st))
+        elif not deterministic_dlatent:
             with _timed("xbar_scatter"):
                 check(L.stpde_lig_xbar_scatter(C.byref(xd), ab, wt, ptr(cell), ptr(dlatent), st))
         else:
@@ -798,15 +847,22 @@ def _per_point_bytes(meta):
     """(forward stash, backward scratch) bytes per query point of the jet path, from the SAME size functions the chunk
     allocators use (``_buf_floats`` / ``_adj_floats``: fp32 blocks or the packed formats of the bf16 mode), plus the
     fragment images of the augmented input (X, XR), the interpolation coefficients, the per-row weights of a combined
-    second-order stream and the cell index.  Tile = 2 points."""
+    second-order stream and the cell index.  A point owns 8 of a tile's 16 rows (tile = 2 points); on a dim = 1, 2, 4 grid
+    2^dim of them, i.e. 2^dim / 16 tiles, and the per-point extras are the row weights, the cell id and the sort scratch
+    (the up to 3 + 1 padding tiles of a chunk, ``nd_tiles``, are not counted: the plan keeps 15 % of headroom)."""
     plan = meta.plan
     mt0 = plan.layers[0]["MT"]
     cp = (plan.cin + 3) // 4 * 4
+    rows = 8 if plan.dim == 3 else 1 << plan.dim
     fwd_tile = 4 * (sum(_buf_floats(meta, l, 1) for l in range(1, 6)) + mt0 * _FRAG + XT * _FRAG)
-    fwd = fwd_tile // 2 + 4 * 16 + (4 * 8 if meta.cfg_out.combo else 0) + 4
     bwd_tile = 4 * (_adj_floats(meta, 2, 1) + _adj_floats(meta, 3, 1) + mt0 * 48)
     if meta.packed_mask:
         bwd_tile += 4 * (_adj_floats(meta, 1, 1) + _adj_floats(meta, 4, 1) + _adj_floats(meta, 0, 1))
+    if plan.dim != 3:
+        fwd = fwd_tile * rows // 16 + 4 * rows                     # + the corner weight of every row
+        bwd = bwd_tile * rows // 16 + rows * cp * 4 + 4 + 4 + 24   # per-row latent adjoints, cell id, permutation, sort scratch
+        return fwd, bwd
+    fwd = fwd_tile // 2 + 4 * 16 + (4 * 8 if meta.cfg_out.combo else 0) + 4
     bwd = bwd_tile // 2 + 8 * cp * 4 + 4 + 24          # per-row latent adjoints, permutation, radix-sort scratch
     return fwd, bwd
 
@@ -852,6 +908,10 @@ def _recompute_chunk(meta, device):
     n = max(1, int(0.5 * _avail_bytes(meta, device) / (fwd + bwd + two)))
     c = 1 << (n.bit_length() - 1)
     mult = 8 if meta.S == 1 else 2
+    if meta.plan.dim != 3:
+        # whole value-tile passes (4 row tiles of 16 >> dim points), and at most the row tiles of the dim = 3 default chunk
+        mult = 4 * (16 >> meta.plan.dim)
+        return max(mult, min(c, (DEFAULT_CHUNK // 2) * (16 >> meta.plan.dim)))
     return max(mult, min(c, DEFAULT_CHUNK))
 
 
@@ -1086,10 +1146,15 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
     memory_budget: bytes the stash + backward scratch of this call may take (None = module setting ``memory_budget``, whose
     None means the free device memory); above it the backward recomputes the forward chunk by chunk (``_recompute_chunk``).
 
-    imnet.dim = 1, 2 or 4 (latent_grid [b, n_1..n_d, c], query_pts [b, p, d], d + c + 1 <= 36): VALUE-ONLY queries --
-    first=False, pairs=(), no combo, and nothing that needs a gradient (call it under ``torch.no_grad()`` or with no input /
-    parameter requiring grad); fp32 or fp32x3 operands.  Returns (jets [1, n_out, b*p], []).  Everything else on such grids
-    is the composed formulation of local_implicit_grid.py.
+    imnet.dim = 1, 2 or 4 (latent_grid [b, n_1..n_d, c], query_pts [b, p, d], d + c + 1 <= 36): VALUE queries --
+    first=False, pairs=(), no combo; fp32 or fp32x3 operands.  Returns (jets [1, n_out, b*p], []).  By default nothing may
+    need a gradient (call it under ``torch.no_grad()`` or with no input / parameter requiring grad).  With ``nd_backward``
+    (``set_nd_backward(True)`` / STPDE_ND_BACKWARD=1) the result is differentiable w.r.t. the latent grid and the IM-NET
+    parameters (a learnable swish beta included) for in_features <= 32: the S = 1 layer / weight-gradient kernels of the
+    dim = 3 value path between stpde_lig_reduce_nd_bwd, stpde_lig_cell_nd and stpde_lig_dlatent_reduce_nd.  d latent on these
+    grids is always the deterministic per-node sum (``deterministic_dlatent = False`` is ignored; there is no atomic variant),
+    the one-call pipeline (``use_pipeline``) stays dim = 3 only, and there are no coordinate derivatives and no point
+    gradients (query_pts is detached).  Everything else on such grids is the composed formulation of local_implicit_grid.py.
     """
     if not (latent_grid.is_cuda and query_pts.is_cuda):
         raise RuntimeError("the HIP jet path needs CUDA/HIP tensors (no CPU fallback)")
@@ -1183,8 +1248,12 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
     meta.need_grad = torch.is_grad_enabled() and (lat.requires_grad or any(p.requires_grad for p in params)
                                                   or (prm_tensor is not None and prm_tensor.requires_grad))
     if dim != 3 and meta.need_grad:
-        raise NotImplementedError("dim = %d queries run in HIP as value-only forward passes: call under torch.no_grad() or "
-                                  "without inputs / parameters that require grad" % dim)
+        if not nd_backward:
+            raise NotImplementedError("dim = %d queries run in HIP as value-only forward passes: call under torch.no_grad() or "
+                                      "without inputs / parameters that require grad" % dim)
+        if plan.cin > ND_TRAIN_MAX_CHANNELS:
+            raise NotImplementedError("dim = %d training backward in HIP takes in_features <= %d (the latent-adjoint kernel "
+                                      "serves two 16-channel tiles)" % (dim, ND_TRAIN_MAX_CHANNELS))
     jets = LigJetFunction.apply(meta, lat, pts, prm_tensor, *params)
     if pad:
         jets = jets[:, :, :P]

@@ -6,7 +6,8 @@ is called from inside ``PDELayer.__call__`` (which announces the derivatives its
 gather -> MLP -> corner-weighted sum, INCLUDING the coordinate derivatives, runs in the HIP jet kernels
 (lig_jet.py).  A plain call (no PDE layer) on the same kind of inputs runs the value-only HIP path.
 Value-only queries on 1-, 2- and 4-d grids (no jet request, nothing that needs a gradient) run in HIP as well: a gather and
-a corner sum of their own around the same IM-NET layer kernels (``_nd_value_eligible``).
+a corner sum of their own around the same IM-NET layer kernels (``_nd_value_eligible``).  With ``lig_jet.nd_backward``
+(opt-in) such a query also trains in HIP: gradients w.r.t. the latent grid and the IM-NET parameters (``_nd_train_eligible``).
 Other decoders / dimensions / requests use the generic composed formulation.
 """
 import threading
@@ -63,8 +64,9 @@ def _nd_value_eligible(model, latent_grid, query_pts, req=None):
     out_features <= 16, the augmented input [r(d); latent(c); 1] within the 36 slots of the layer kernels' input image
     (c <= 34 / 33 / 31 for d = 1 / 2 / 4 -- the reference's own 4-d test case, c = 32, is one channel too wide and stays on
     the composed formulation), every grid axis >= 2 nodes, fp32 or fp32x3 operands, no jet request for these points and
-    nothing that needs a gradient (no_grad, or no input / parameter requiring grad).  Jets, training backward and point
-    gradients on such grids keep the composed formulation."""
+    nothing that needs a gradient (no_grad, or no input / parameter requiring grad).  Jets and point gradients on such grids
+    keep the composed formulation; so does the training backward unless ``lig_jet.nd_backward`` is switched on
+    (``_nd_train_eligible``)."""
     if not isinstance(model, ImNet) or model.dim not in lig_jet.ND_VALUE_DIMS:
         return False
     d = model.dim
@@ -84,6 +86,26 @@ def _nd_value_eligible(model, latent_grid, query_pts, req=None):
                                     or any(p.requires_grad for p in model.parameters())):
         return False
     return True
+
+
+def _nd_train_eligible(model, latent_grid, query_pts, req=None):
+    """A value query on a 1-, 2- or 4-d grid whose TRAINING BACKWARD the HIP path serves (opt-in: ``lig_jet.nd_backward``,
+    ``lig_jet.set_nd_backward`` / STPDE_ND_BACKWARD=1; off, this is always False and such a query is composed, as before):
+    grad mode on and the latent grid and / or an IM-NET parameter (a learnable swish beta included) requires grad; everything
+    ``_nd_value_eligible`` asks for other than its gradient clause (ImNet decoder itself -- not an nn.DataParallel over
+    several devices --, CUDA fp32, nf a multiple of 16, out_features <= 16, d + in_features + 1 <= 36, every axis >= 2 nodes,
+    fp32 or fp32x3 operands -- not bf16 --, no jet request for these points); in_features <= 32 (the latent-adjoint kernel
+    k_xbar<XL> exists for XL = 1, 2, so d = 1 with c = 33, 34 and d = 2 with c = 33 stay composed whenever a gradient is
+    needed); and the points themselves carry no gradient.  d latent is the deterministic per-node sum on these grids, whatever
+    ``lig_jet.deterministic_dlatent`` says."""
+    if not lig_jet.nd_backward or not torch.is_grad_enabled() or query_pts.requires_grad:
+        return False
+    with torch.no_grad():                   # = _nd_value_eligible without its gradient clause
+        if not _nd_value_eligible(model, latent_grid, query_pts, req):
+            return False
+    if model.in_features > lig_jet.ND_TRAIN_MAX_CHANNELS:
+        return False
+    return bool(latent_grid.requires_grad or any(p.requires_grad for p in model.parameters()))
 
 
 def _xmin_is_zero(xmin, xmax=None, shape3=None):
@@ -170,7 +192,7 @@ def query_local_implicit_grid(model, latent_grid, query_pts, xmin, xmax):
             jets, _ = lig_jet.lig_jets(model, latent_grid, query_pts, xmin, xmax, False, ())
             stats["hip_value_calls"] += 1
             return jets[0].t().reshape(query_pts.shape[0], query_pts.shape[1], jets.shape[1])
-    if _nd_value_eligible(model, latent_grid, query_pts, req) \
+    if (_nd_value_eligible(model, latent_grid, query_pts, req) or _nd_train_eligible(model, latent_grid, query_pts, req)) \
             and _xmin_is_zero(xmin, xmax, tuple(latent_grid.shape[1:-1])):
         jets, _ = lig_jet.lig_jets(model, latent_grid, query_pts, xmin, xmax, False, ())
         stats["hip_value_calls"] += 1

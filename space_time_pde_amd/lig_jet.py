@@ -12,6 +12,8 @@ Everything here is plumbing (buffer allocation, weight packing by index gather, 
 query points runs in the HIP library.  There is no fallback: tensors must be CUDA/HIP float32.
 """
 import ctypes as C
+import dataclasses
+import math
 import os
 import threading
 
@@ -354,45 +356,149 @@ def cached_box_constants(shape3, xmin, xmax):
 # ------------------------------------------------------------------------------------------------------------
 # the autograd function
 # ------------------------------------------------------------------------------------------------------------
-class _Meta:
-    pass
+def _tail_applies(fused_tail, nf, cfg, combo, value_tiles=False):
+    """THE predicate of the fused fc3 -> fc4 -> fc5 kernels: the switch, the reference widths, and a training stream set they are
+    compiled for (a combined second-order stream needs its per-row weights) or the value-tile pass of a forward-only value query."""
+    return bool(fused_tail and nf in (16, 32) and (value_tiles or ((cfg.S1, cfg.S2) in TAIL_SETS and (cfg.S2 != 1 or combo))))
 
 
-def _AW():
+@dataclasses.dataclass(frozen=True, eq=False)
+class JetCall:
+    """What one jet call is and how it runs, decided ONCE when the call is made (``JetCall.make``) and read by every later
+    stage: the forward, its chunks, the backward and a stash rebuild inside the backward.  Frozen -- except ``chunk``."""
+    # ---- plan and request
+    plan: ImNetPlan         # layout of the IM-NET architecture
+    cfg: JetCfg             # streams the layer kernels carry
+    cfg_out: JetCfg         # streams the caller gets (second-order ones of a piecewise-linear activation come from the reduction)
+    cfg_val: JetCfg         # the value stream alone (layer-0 weight gradient of the split layer-0 adjoint)
+    S: int                  # number of MLP streams
+    S_out: int              # number of output streams
+    pairs: list             # padded second-derivative pairs of the output streams (["combo"]: one combined stream)
+    # ---- operands
+    bf16: bool              # bf16 A-operand packs of the hidden-to-hidden weights exist ("bf16" and "fp32x3")
+    nsplit: int             # bf16 terms per weight: 1, or 3 = the exact split of "fp32x3"
+    packed_mask: int        # bit l: the buffer of layer l's rows is PACKED (bit 0: the layer-0 value adjoint); 31 or 0
+    # ---- geometry
+    B: int                  # batch
+    N: int                  # query points per batch entry
+    grid_shape: tuple       # nodes per axis of the latent grid
+    lo_c: list              # clamp bounds and cell size per axis (box_constants)
+    hi_c: list
+    cube: list
+    P_pad: int              # B * N padded to whole tiles / value-tile passes
+    # ---- memory plan
+    budget: object          # bytes the stash + scratch of the call may take (None: the free device memory)
+    recompute: bool         # keep no stash, rebuild it in the backward (``force_recompute``)
+    chunk: int              # points per launch chunk; the ONE field written after construction, through plan_chunk only: by the
+    #                         memory plan of LigJetFunction.forward (and by lig_jets for the device-dependent n-D default)
+    # ---- gradient need
+    need_grad: bool         # a backward can follow (grad mode was on and an input requires grad)
+    # ---- switches, frozen when the call is made
+    det: bool               # _lib.deterministic: dW in long accumulators
+    det_dlatent: bool       # d latent as a per-node sum in a fixed order (False: atomic scatter)
+    value_tiles: bool       # forward-only value queries on the value-tile kernels
+    tan0_rowsum: bool       # layer-0 tangent adjoints as per-tile row sums
+    wgrad_split: bool       # "fp32x3": weight gradients on the split operands too
+    fused_tail: bool        # fc3 -> fc5 in one kernel where ``tail`` / a value-tile pass allows
+    fc1_fused: bool         # bf16 mode: fused backward of the first hidden layer (STPDE_FC1_FUSED)
+    nd_backward: bool       # dim = 1, 2, 4: the HIP training backward is allowed
+    pipeline: bool          # driver: one library call per direction (dim = 3, no per-kernel profile), else kernel by kernel
+    # ---- derived, computed once
+    tail: bool              # the fused fc3 -> fc5 kernels serve this call's training stream set (_tail_applies)
+    SP0: int                # streams of the layer-0 adjoint: value (+ 3 tangents)
+    split0: bool            # ... kept as value blocks + tangent row sums
+    mult: int               # points a launch chunk is a multiple of
+
+    @classmethod
+    def make(cls, plan, act, act_param, first, pairs, combo, precision, grid_shape, box, budget=None, B=1, N=0,
+             chunk_points=None, need_grad=True):
+        """The record of a call: needs no device.  box = (lo_c, hi_c, cube); precision / budget None: the module settings.  Reads
+        ``_lib.deterministic`` and the module switches -- the only place of this module that does."""
+        precision = precision or mlp_precision
+        if precision not in ("fp32", "bf16", "fp32x3"):
+            raise ValueError("mlp precision must be 'fp32', 'bf16' or 'fp32x3'")
+        dim = plan.dim
+        if dim != 3 and precision == "bf16":
+            # (the value-tile kernels have no one-term bf16 variant; local_implicit_grid routes such a query to the composed ops)
+            raise NotImplementedError("dim = %d value queries run with fp32 or fp32x3 operands" % dim)
+        # output streams (what the caller gets) vs MLP streams (what the layer kernels carry): for piecewise-linear
+        # activations sigma'' = 0 makes every second-order MLP stream identically zero, so only value + gradient streams
+        # go through the network and the reduction supplies the second derivatives from the weight cross terms
+        cfg_out, S_out, ppairs = make_cfg(act, act_param, first, list(pairs), combo)
+        cfg, S = cfg_out, S_out
+        if act in ("relu", "leakyrelu") and ppairs:
+            cfg, S, _ = make_cfg(act, act_param, True, [])
+        tail = _tail_applies(fused_tail, plan.nf, cfg, cfg_out.combo)
+        # bf16 mode, reference width: the stashes of the hidden layers' output rows and their adjoints in the PACKED form -- all
+        # of their consumers are bf16-operand kernels (layers 1-2: k_layer_coop / k_wgrad_coop; fc3 -> fc5: k_tail_fwd_bf /
+        # k_tail_bwd_bf and the bf16 variant of k_wgrad_wave).  ``packed_stash = False``: fp32 blocks, fp32 MFMA in fc3 -> fc5.
+        # (S > 6 is not served by the bf16 kernels; the packed buffer of fc2's rows is read by the fused fc3 -> fc5 kernels.)
+        # Bits 1-4: the layer buffers of fc1 ... fc4's rows; bit 0: the value-stream adjoint of layer 0 as bf16 blocks (needs
+        # the tangent row sums: value-only adjoint).  The library serves "all of them" or none.
+        packed = (precision == "bf16" and packed_stash and plan.nf == 32 and S <= 6 and tail and cfg.S1 == 3 and tan0_rowsum)
+        # tiles hold 2 points, value-only queries run whole value-tile passes (4 tiles).  dim = 1, 2, 4: 16 >> dim points per
+        # tile, whole passes; the gather pads the last tiles of a chunk itself (nd_tiles), the points are not padded; default
+        # chunk there: the row TILES of the dim = 3 chunk, which lig_jets cuts down to what the device has free
+        mult = (8 if S == 1 else 2) if dim == 3 else 4 * (16 >> dim)
+        chunk_points = chunk_points or (DEFAULT_CHUNK if dim == 3 else (DEFAULT_CHUNK // 2) * (16 >> dim))
+        P, SP0 = B * N, 1 + cfg.S1
+        return cls(plan=plan, cfg=cfg, cfg_out=cfg_out, cfg_val=make_cfg(act, act_param, False, [])[0], S=S, S_out=S_out,
+                   pairs=ppairs, bf16=precision in ("bf16", "fp32x3"), nsplit=3 if precision == "fp32x3" else 1,
+                   packed_mask=31 if packed else 0, B=B, N=N, grid_shape=tuple(grid_shape), lo_c=box[0], hi_c=box[1],
+                   cube=box[2], P_pad=P + ((-P) % mult if dim == 3 else 0),
+                   budget=budget if budget is not None else memory_budget, recompute=bool(force_recompute),
+                   chunk=max(mult, chunk_points // mult * mult), need_grad=bool(need_grad), det=bool(_lib.deterministic),
+                   det_dlatent=bool(deterministic_dlatent), value_tiles=bool(value_tiles), tan0_rowsum=bool(tan0_rowsum),
+                   wgrad_split=bool(wgrad_split), fused_tail=bool(fused_tail), fc1_fused=fc1_fused_enabled(),
+                   nd_backward=bool(nd_backward), pipeline=bool(use_pipeline and profile is None and dim == 3),
+                   tail=tail, SP0=SP0, split0=bool(SP0 == 4 and tan0_rowsum), mult=mult)
+
+    def plan_chunk(self, points):
+        """the one write of the record: ``chunk``, by the memory plan (LigJetFunction.forward; lig_jets: the n-D default)"""
+        object.__setattr__(self, "chunk", points)
+
+
+def _AW(call):
     """floats of storage per accumulated dW element: 1, or -- deterministic mode -- a long accumulator (_lib.DET_K int64)"""
-    return 2 * _lib.DET_K if _lib.deterministic else 1
+    return 2 * _lib.DET_K if call.det else 1
 
 
-def _layer_desc(ntiles, lay, cfg, first_hidden, bf16=0, packed=0):
+def _dw_slice(call, dw_flat, l):
+    """layer l's part of the flat dW buffer"""
+    off, mp, ka = call.plan.dw_off[l]
+    return dw_flat[_AW(call) * off:_AW(call) * (off + mp * ka)]
+
+
+def _layer_desc(call, ntiles, lay, cfg, first_hidden, bf16=0, packed=0):
     d = LayerDesc()
     d.ntiles, d.KT, d.MT, d.first_hidden, d.cfg = ntiles, lay["KT"], lay["MT"], int(first_hidden), cfg
     d.mfma_bf16 = int(bf16)
     d.packed = int(packed)
-    d.det = int(_lib.deterministic)      # (read by the weight-gradient entry points only)
+    d.det = int(call.det)      # (read by the weight-gradient entry points only)
     return d
 
 
-def _buf_floats(meta, l, nt):
+def _buf_floats(call, l, nt):
     """floats of the layer buffer of layer l's output rows for nt row tiles: [S][MT] fp32 blocks, or the PACKED form (bf16
     mode: value stream fp32, derivative streams bf16; include/stpde_hip.h, stpde_layer_desc.packed)."""
-    mt = meta.plan.layers[l]["MT"]
-    if (meta.packed_mask >> l) & 1:
-        return nt * mt * (256 + (meta.S - 1) * 128)
-    return nt * meta.S * mt * _FRAG
+    mt = call.plan.layers[l]["MT"]
+    if (call.packed_mask >> l) & 1:
+        return nt * mt * (256 + (call.S - 1) * 128)
+    return nt * call.S * mt * _FRAG
 
 
-def _adj_floats(meta, l, nt):
+def _adj_floats(call, l, nt):
     """floats of the adjoint buffer of layer l's output rows: the size of the layer buffer, or -- packed mode -- a packed
     ADJOINT buffer, every stream bf16 (layer 0: its value stream only)."""
-    mt = meta.plan.layers[l]["MT"]
-    if (meta.packed_mask >> l) & 1:
-        return nt * (meta.S if l else 1) * mt * 128
-    return nt * mt * _FRAG if l == 0 else _buf_floats(meta, l, nt)
+    mt = call.plan.layers[l]["MT"]
+    if (call.packed_mask >> l) & 1:
+        return nt * (call.S if l else 1) * mt * 128
+    return nt * mt * _FRAG if l == 0 else _buf_floats(call, l, nt)
 
 
-def _pk(meta, l, writes):
+def _pk(call, l, writes):
     """stpde_layer_desc.packed of a call on layer l that writes the buffer of layer `writes` (-1: none)."""
-    m = meta.packed_mask
+    m = call.packed_mask
     return (1 if (l >= 2 and (m >> (l - 1)) & 1) else 0) | (2 if (writes >= 0 and (m >> writes) & 1) else 0) | \
         (4 if (m >> l) & 1 else 0)
 
@@ -408,8 +514,8 @@ def _dp(t):
     return None if t is None else t.data_ptr()
 
 
-def _plan_desc(meta, packs):
-    plan = meta.plan
+def _plan_desc(call, packs, packs16):
+    plan = call.plan
     d = ImNetPlanDesc()
     d.nlayers, d.cin, d.cout, d.nf16 = 6, plan.cin, plan.cout, plan.nf // 16
     pv = plan.pack_view
@@ -418,52 +524,45 @@ def _plan_desc(meta, packs):
         if lay["KT"]:
             d.Wh[l], d.WhT[l] = pv(packs, l, "Wh").data_ptr(), pv(packs, l, "WhT").data_ptr()
         d.Ws[l], d.WsL[l], d.tanc[l] = (pv(packs, l, n).data_ptr() for n in ("Ws", "WsL", "tanc"))
-        if meta.packs16:
-            d.Wh16[l], d.WhT16[l] = _dp(meta.packs16.get((l, "Wh"))), _dp(meta.packs16.get((l, "WhT")))
+        if packs16:
+            d.Wh16[l], d.WhT16[l] = _dp(packs16.get((l, "Wh"))), _dp(packs16.get((l, "WhT")))
         d.dw_off[l] = plan.dw_off[l][0]
-    d.mfma_bf16 = meta.nsplit if meta.packs16 else 0
-    d.packed_mask = meta.packed_mask
+    d.mfma_bf16 = call.nsplit if packs16 else 0
+    d.packed_mask = call.packed_mask
     return d
 
 
-def _gather_desc(meta, latent, Pc, p0):
+def _gather_desc(call, latent, Pc, p0):
     gd = GatherDesc()
-    gd.P, gd.N, gd.B = Pc, meta.N, meta.B
+    gd.P, gd.N, gd.B = Pc, call.N, call.B
     gd.n0, gd.n1, gd.n2, gd.C = latent.shape[1], latent.shape[2], latent.shape[3], latent.shape[4]
     for k in range(3):
-        gd.lo_c[k], gd.hi_c[k], gd.cube[k] = meta.lo_c[k], meta.hi_c[k], meta.cube[k]
+        gd.lo_c[k], gd.hi_c[k], gd.cube[k] = call.lo_c[k], call.hi_c[k], call.cube[k]
     gd.p_base = p0
     for k in range(6):
-        gd.alpha[k] = meta.cfg_out.alpha[k]
+        gd.alpha[k] = call.cfg_out.alpha[k]
     return gd
 
 
-def _flags(meta, need_grad):
-    f = 0
-    if need_grad:
-        f |= _lib.F_STASH
-    if value_tiles:
-        f |= _lib.F_VALUE_TILES
-    if fused_tail:
-        f |= _lib.F_FUSED_TAIL
-    if tan0_rowsum:
-        f |= _lib.F_TAN0_ROWSUM
-    if deterministic_dlatent:
-        f |= _lib.F_DETERMINISTIC
-    if meta.need_wgrad:
-        f |= _lib.F_WGRAD
-    if not wgrad_split:
-        f |= _lib.F_WGRAD_FP32
-    if not fc1_fused_enabled():
-        f |= _lib.F_NO_FC1_FUSED
-    if _lib.deterministic:
-        f |= _lib.F_DET
-    return f
+def _flags(call, need_grad, need_wgrad=True):
+    """STPDE_F_* of the one-call entry points (the forward reads F_STASH, F_VALUE_TILES and F_FUSED_TAIL only)"""
+    bits = ((need_grad, _lib.F_STASH), (call.value_tiles, _lib.F_VALUE_TILES), (call.fused_tail, _lib.F_FUSED_TAIL),
+            (call.tan0_rowsum, _lib.F_TAN0_ROWSUM), (call.det_dlatent, _lib.F_DETERMINISTIC), (need_wgrad, _lib.F_WGRAD),
+            (not call.wgrad_split, _lib.F_WGRAD_FP32), (not call.fc1_fused, _lib.F_NO_FC1_FUSED), (call.det, _lib.F_DET))
+    return sum(bit for on, bit in bits if on)
 
 
-def _forward_chunk_c(meta, packs, latent, pts_c, jets, p0, need_grad=True):
+def _dlatent_scratch(call, rows, Pc, dev):
+    """Scratch of one chunk's deterministic d latent -> (adjoints of ``rows`` rows, permutation of the Pc points sorted by cell,
+    first sorted point of every grid node, temporary storage of the sort in bytes, number of nodes)."""
+    n_nodes = call.B * math.prod(call.grid_shape)
+    nb = int(_lib.lib().stpde_lig_sort_tmp_bytes(Pc, n_nodes))
+    return (torch.empty(rows * ((call.plan.cin + 3) // 4 * 4), device=dev), torch.empty(Pc, device=dev, dtype=torch.int32),
+            torch.empty(n_nodes + 1, device=dev, dtype=torch.int32), torch.empty(nb, device=dev, dtype=torch.uint8), n_nodes)
+
+
+def _forward_chunk_c(call, packs, packs16, latent, pts_c, jets, p0, need_grad=True):
     """_forward_chunk through ONE library call: this function only allocates the chunk's buffers."""
-    plan, S = meta.plan, meta.S
     Pc = pts_c.shape[0]
     nt = Pc // 2
     dev = pts_c.device
@@ -471,25 +570,25 @@ def _forward_chunk_c(meta, packs, latent, pts_c, jets, p0, need_grad=True):
     s = dict(p0=p0, Pc=Pc, ws=ws)
     s["X"] = torch.empty(nt * XT * _FRAG, device=dev)
     s["XR"] = None      # (round 5: no row-major copy of X any more -- the weight-gradient kernels transpose the fragments they need)
-    s["cw"] = torch.empty(Pc * 8, device=dev) if meta.cfg_out.combo else None
+    s["cw"] = torch.empty(Pc * 8, device=dev) if call.cfg_out.combo else None
     s["coef"] = torch.empty(Pc * 16, device=dev)
     s["cell"] = torch.empty(Pc, device=dev, dtype=torch.int32)
-    s["bufs"] = [None] + [torch.empty(_buf_floats(meta, l, nt), device=dev) for l in range(1, 6)]
-    s["z0"] = torch.empty(nt * plan.layers[0]["MT"] * _FRAG, device=dev) if need_grad else None
+    s["bufs"] = [None] + [torch.empty(_buf_floats(call, l, nt), device=dev) for l in range(1, 6)]
+    s["z0"] = torch.empty(nt * call.plan.layers[0]["MT"] * _FRAG, device=dev) if need_grad else None
     ws.X, ws.XR, ws.coef, ws.cw, ws.cell = (_dp(s[k]) for k in ("X", "XR", "coef", "cw", "cell"))
     ws.pre[0] = _dp(s["z0"])
     for l in range(1, 6):
         ws.pre[l] = s["bufs"][l].data_ptr()
-    pd = _plan_desc(meta, packs)
-    gd = _gather_desc(meta, latent, Pc, p0)
-    check(_lib.lib().stpde_lig_imnet_jet_fwd(C.byref(pd), C.byref(meta.cfg), C.byref(meta.cfg_out), C.byref(gd), ptr(pts_c),
+    pd = _plan_desc(call, packs, packs16)
+    gd = _gather_desc(call, latent, Pc, p0)
+    check(_lib.lib().stpde_lig_imnet_jet_fwd(C.byref(pd), C.byref(call.cfg), C.byref(call.cfg_out), C.byref(gd), ptr(pts_c),
                                              ptr(latent), C.byref(ws), C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2],
-                                             _flags(meta, need_grad), stream_ptr()))
+                                             _flags(call, need_grad), stream_ptr()))
     s["gd"] = gd
     return s
 
 
-def _backward_chunk_c(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar=None, after_dlatent=None):
+def _backward_chunk_c(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pbar=None, after_dlatent=None):
     """_backward_chunk through ONE library call (+ allocation of its scratch).
 
     after_dlatent (callable or None): "dgrad-first" order in TWO calls -- phase A runs the whole input-gradient chain into
@@ -497,7 +596,6 @@ def _backward_chunk_c(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar=None,
     d latent there), phase B computes the remaining weight gradients while that all-reduce is in flight.  (Both phases on the
     current stream.  Round 4's variant with phase B on a side stream, so that the U-Net backward ran beside it, measured slower
     -- profiles/r4_overlap_timeline.txt -- and was deleted in round 6.)"""
-    plan, S = meta.plan, meta.S
     Pc, ws, gd = saved["Pc"], saved["ws"], saved["gd"]
     nt = Pc // 2
     dev = saved["X"].device
@@ -508,42 +606,39 @@ def _backward_chunk_c(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar=None,
         keep.append(t)
         return t.data_ptr()
 
-    MT0 = plan.layers[0]["MT"]
-    SP0 = 1 + meta.cfg.S1
-    ws.abar2x, ws.abar3x = buf(_adj_floats(meta, 2, nt)), buf(_adj_floats(meta, 3, nt))
-    if meta.packed_mask:        # packed ADJOINT buffers are a format of their own: none of them goes over a stash
-        ws.abar1x, ws.abar4x = buf(_adj_floats(meta, 1, nt)), buf(_adj_floats(meta, 4, nt))
-        if meta.packed_mask & 1:
-            ws.abar0x = buf(_adj_floats(meta, 0, nt))
-    ws.tan0 = buf(nt * MT0 * 48) if (SP0 == 4 and tan0_rowsum) else None
-    ws.abar0 = buf(nt * SP0 * MT0 * _FRAG) if (SP0 == 4 and not tan0_rowsum) else None
-    if dlatent is not None and deterministic_dlatent:
-        cp = (plan.cin + 3) // 4 * 4
-        n_nodes = meta.B * meta.grid_shape[0] * meta.grid_shape[1] * meta.grid_shape[2]
-        ws.xrows = buf(Pc * 8 * cp)
-        ws.perm, ws.start = buf(Pc, torch.int32), buf(n_nodes + 1, torch.int32)
-        nb = int(_lib.lib().stpde_lig_sort_tmp_bytes(Pc, n_nodes))
-        ws.sort_tmp, ws.sort_tmp_bytes = buf(nb, torch.uint8), nb
-    pd = _plan_desc(meta, packs)
-    flags = _flags(meta, True)
-    two_phase = (after_dlatent is not None and fused_tail and tan0_rowsum and plan.nf in (16, 32) and SP0 in (1, 4)
-                 and (meta.cfg.S1, meta.cfg.S2) in TAIL_SETS and (meta.cfg.S2 != 1 or saved["cw"] is not None))
+    MT0 = call.plan.layers[0]["MT"]
+    ws.abar2x, ws.abar3x = buf(_adj_floats(call, 2, nt)), buf(_adj_floats(call, 3, nt))
+    if call.packed_mask:        # packed ADJOINT buffers are a format of their own: none of them goes over a stash
+        ws.abar1x, ws.abar4x = buf(_adj_floats(call, 1, nt)), buf(_adj_floats(call, 4, nt))
+        if call.packed_mask & 1:
+            ws.abar0x = buf(_adj_floats(call, 0, nt))
+    ws.tan0 = buf(nt * MT0 * 48) if call.split0 else None
+    ws.abar0 = buf(nt * call.SP0 * MT0 * _FRAG) if (call.SP0 == 4 and not call.split0) else None
+    if dlatent is not None and call.det_dlatent:
+        scratch = _dlatent_scratch(call, Pc * 8, Pc, dev)[:4]
+        keep += scratch
+        ws.xrows, ws.perm, ws.start, ws.sort_tmp = (t.data_ptr() for t in scratch)
+        ws.sort_tmp_bytes = scratch[3].numel()
+    pd = _plan_desc(call, packs, packs16)
+    flags = _flags(call, True, dw_flat is not None)
+    # (the stream sets of ``tail`` have SP0 = 1 or 4, what the two-phase order is compiled for)
+    two_phase = after_dlatent is not None and call.tail and call.tan0_rowsum
 
-    def call(fl):
-        check(_lib.lib().stpde_lig_imnet_jet_bwd(C.byref(pd), C.byref(meta.cfg), C.byref(meta.cfg_out), C.byref(meta.cfg_val),
+    def launch(fl):
+        check(_lib.lib().stpde_lig_imnet_jet_bwd(C.byref(pd), C.byref(call.cfg), C.byref(call.cfg_out), C.byref(call.cfg_val),
                                                  C.byref(gd), C.byref(ws), C.c_void_p(jets_bar.data_ptr() + 4 * saved["p0"]),
                                                  jets_bar.shape[2], ptr(dw_flat), ptr(dlatent), ptr(pbar), fl, stream_ptr()))
 
     if two_phase:
-        if not meta.packed_mask:
+        if not call.packed_mask:
             ws.abar1x = buf(saved["bufs"][1].numel())
-        if not meta.packed_mask & 1:
+        if not call.packed_mask & 1:
             ws.abar0x = buf(nt * MT0 * _FRAG)
-        call(flags | _lib.F_PHASE_A)
+        launch(flags | _lib.F_PHASE_A)
         after_dlatent()
-        call(flags | _lib.F_PHASE_B)
+        launch(flags | _lib.F_PHASE_B)
     else:
-        call(flags)
+        launch(flags)
         if after_dlatent is not None:
             after_dlatent()
     return None
@@ -556,20 +651,20 @@ def nd_tiles(P, dim):
     return (-(-P // tp) + 3) // 4 * 4
 
 
-def _gather_nd_desc(meta, latent, Pc, p0, nt):
+def _gather_nd_desc(call, latent, Pc, p0, nt):
     gd = GatherNdDesc()
-    gd.D, gd.P, gd.N, gd.B, gd.C, gd.p_base, gd.ntiles = meta.plan.dim, Pc, meta.N, meta.B, latent.shape[-1], p0, nt
-    for k in range(meta.plan.dim):
-        gd.n[k], gd.lo_c[k], gd.hi_c[k], gd.cube[k] = latent.shape[1 + k], meta.lo_c[k], meta.hi_c[k], meta.cube[k]
+    gd.D, gd.P, gd.N, gd.B, gd.C, gd.p_base, gd.ntiles = call.plan.dim, Pc, call.N, call.B, latent.shape[-1], p0, nt
+    for k in range(call.plan.dim):
+        gd.n[k], gd.lo_c[k], gd.hi_c[k], gd.cube[k] = latent.shape[1 + k], call.lo_c[k], call.hi_c[k], call.cube[k]
     return gd
 
 
-def _forward_chunk(meta, packs, latent, pts_c, jets, p0, need_grad=True):
+def _forward_chunk(call, packs, packs16, latent, pts_c, jets, p0, need_grad=True):
     """Run gather + layers 1..5 + reduce for points [p0, p0+Pc) ; returns the buffers backward needs."""
-    nd = meta.plan.dim != 3       # value query on a 1-, 2- or 4-d grid: own gather / corner sum, the same layer kernels
-    if use_pipeline and profile is None and not nd:
-        return _forward_chunk_c(meta, packs, latent, pts_c, jets, p0, need_grad)
-    plan, cfg, S = meta.plan, meta.cfg, meta.S
+    nd = call.plan.dim != 3       # value query on a 1-, 2- or 4-d grid: own gather / corner sum, the same layer kernels
+    if call.pipeline:
+        return _forward_chunk_c(call, packs, packs16, latent, pts_c, jets, p0, need_grad)
+    plan, cfg, S = call.plan, call.cfg, call.S
     L = _lib.lib()
     st = stream_ptr()
     Pc = pts_c.shape[0]
@@ -577,26 +672,17 @@ def _forward_chunk(meta, packs, latent, pts_c, jets, p0, need_grad=True):
     dev = pts_c.device
     X = torch.empty(nt * XT * _FRAG, device=dev)
     XR = None           # (round 5: no row-major copy of X; the weight-gradient kernels read X)
-    cw = torch.empty(Pc * 8, device=dev) if meta.cfg_out.combo else None
+    cw = torch.empty(Pc * 8, device=dev) if call.cfg_out.combo else None
     coef = cell = roww = None
     if nd:
-        if S != 1 or (need_grad and not nd_backward):
-            raise NotImplementedError("dim = %d queries run in HIP as value-only forward passes" % plan.dim)
         roww = torch.empty(nt * 16, device=dev)       # corner weight of every row (cw of stpde_lig_gather_nd)
-        gd = _gather_nd_desc(meta, latent, Pc, p0, nt)
+        gd = _gather_nd_desc(call, latent, Pc, p0, nt)
         with _timed("gather_nd"):
             check(L.stpde_lig_gather_nd(C.byref(gd), ptr(pts_c), ptr(latent), ptr(X), ptr(roww), st))
     else:
         coef = torch.empty(Pc * 16, device=dev)
         cell = torch.empty(Pc, device=dev, dtype=torch.int32)
-        gd = GatherDesc()
-        gd.P, gd.N, gd.B = Pc, meta.N, meta.B
-        gd.n0, gd.n1, gd.n2, gd.C = latent.shape[1], latent.shape[2], latent.shape[3], latent.shape[4]
-        for k in range(3):
-            gd.lo_c[k], gd.hi_c[k], gd.cube[k] = meta.lo_c[k], meta.hi_c[k], meta.cube[k]
-        gd.p_base = p0
-        for k in range(6):
-            gd.alpha[k] = meta.cfg_out.alpha[k]
+        gd = _gather_desc(call, latent, Pc, p0)
         with _timed("gather"):
             check(L.stpde_lig_gather(C.byref(gd), ptr(pts_c), ptr(latent), ptr(X), ptr(XR), ptr(coef), ptr(cell),
                                      ptr(cw), st))
@@ -606,22 +692,21 @@ def _forward_chunk(meta, packs, latent, pts_c, jets, p0, need_grad=True):
     z0 = None
     # forward-only value queries (inference): VALUE-TILE kernels -- four consecutive row tiles share one pass over the
     # weights (the weight operand is what bounds a one-stream pass); same buffers, a quarter of the "tiles"
-    vt = S == 1 and not need_grad and (not meta.packs16 or meta.nsplit == 3) and nt % 4 == 0 and value_tiles
+    vt = S == 1 and not need_grad and (not packs16 or call.nsplit == 3) and nt % 4 == 0 and call.value_tiles
     lcfg, lnt = cfg, nt
     if vt:
         lcfg = JetCfg()
         lcfg.S1, lcfg.S2, lcfg.act, lcfg.act_param = 0, 3, cfg.act, cfg.act_param
         lnt = nt // 4
     # fc3 -> fc4 -> fc5 in one kernel (inter-layer data in registers) for the reference widths and the training stream sets
-    tail = (fused_tail and plan.nf in (16, 32) and (vt or ((cfg.S1, cfg.S2) in TAIL_SETS
-                                                           and (cfg.S2 != 1 or cw is not None))))
+    tail = _tail_applies(call.fused_tail, plan.nf, cfg, call.cfg_out.combo, vt)
     for l in range(1, 6):
         lay = plan.layers[l]
         if tail and l == 3:
-            outs = [torch.empty(_buf_floats(meta, k, nt), device=dev) for k in (3, 4, 5)]
+            outs = [torch.empty(_buf_floats(call, k, nt), device=dev) for k in (3, 4, 5)]
             arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
-            pk_tail = (meta.packed_mask >> 2) & 1         # bf16 mode: packed buffers on both sides, bf16-operand kernel
-            w16s = arr([meta.packs16[(k, "Wh")] for k in (3, 4, 5)]) if pk_tail else None
+            pk_tail = (call.packed_mask >> 2) & 1         # bf16 mode: packed buffers on both sides, bf16-operand kernel
+            w16s = arr([packs16[(k, "Wh")] for k in (3, 4, 5)]) if pk_tail else None
             with _timed("tail_fwd"):
                 check(L.stpde_jet_tail_fwd_p(C.byref(lcfg), lnt, plan.nf // 16, ptr(prev), ptr(X),
                                              arr([pv(packs, k, "Wh") for k in (3, 4, 5)]),
@@ -630,9 +715,9 @@ def _forward_chunk(meta, packs, latent, pts_c, jets, p0, need_grad=True):
                                              3 if pk_tail else 0, w16s, st))
             bufs += outs
             break
-        out = torch.empty(_buf_floats(meta, l, nt), device=dev)
-        w16 = meta.packs16.get((l, "Wh")) if meta.packs16 else None
-        d = _layer_desc(lnt, lay, lcfg, l == 1, meta.nsplit if w16 is not None else 0, _pk(meta, l, l) & 3)
+        out = torch.empty(_buf_floats(call, l, nt), device=dev)
+        w16 = packs16.get((l, "Wh")) if packs16 else None
+        d = _layer_desc(call, lnt, lay, lcfg, l == 1, call.nsplit if w16 is not None else 0, _pk(call, l, l) & 3)
         if l == 1 and need_grad:
             # value stream of the layer-0 pre-activations, kept for the layer-1 input-gradient kernel (which then writes
             # the layer-0 adjoint over it): reading 2 KB per row back is cheaper than regenerating it on the fp32 MFMA
@@ -654,12 +739,12 @@ def _forward_chunk(meta, packs, latent, pts_c, jets, p0, need_grad=True):
         # the cell ids (stpde_lig_cell_nd) and the row weights for the adjoint of the corner sum
         return dict(X=X, bufs=bufs, z0=z0, roww=roww, pts_c=pts_c, p0=p0, Pc=Pc, nt=nt)
     with _timed("reduce_fwd"):
-        check(L.stpde_lig_reduce_fwd(C.byref(meta.cfg_out), S, Pc, plan.cout, ptr(bufs[5]), ptr(coef),
+        check(L.stpde_lig_reduce_fwd(C.byref(call.cfg_out), S, Pc, plan.cout, ptr(bufs[5]), ptr(coef),
                                      C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2], st))
     return dict(X=X, XR=X, coef=coef, cell=cell, bufs=bufs, p0=p0, Pc=Pc, cw=cw, z0=z0)
 
 
-def _backward_chunk(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar=None, after_dlatent=None):
+def _backward_chunk(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pbar=None, after_dlatent=None):
     """reduce_bwd -> for l = 5..1: wgrad_l (reads abar_l and the still intact pre-activations of layer l-1), then
     dgrad_l (overwrites them with abar_{l-1}) -> wgrad_0 -> xbar/scatter.
 
@@ -667,8 +752,8 @@ def _backward_chunk(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar=None, a
     ``nd_tiles`` row tiles, then xbar_rows -> cell_nd -> cell_sort -> dlatent_reduce_nd.  d latent on these grids is ALWAYS
     the deterministic per-node sum: ``deterministic_dlatent = False`` is ignored, there is no atomic variant."""
     if "ws" in saved:
-        return _backward_chunk_c(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar, after_dlatent)
-    plan, cfg, S = meta.plan, meta.cfg, meta.S
+        return _backward_chunk_c(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pbar, after_dlatent)
+    plan, cfg, S = call.plan, call.cfg, call.S
     L = _lib.lib()
     st = stream_ptr()
     Pc, p0 = saved["Pc"], saved["p0"]
@@ -678,7 +763,7 @@ def _backward_chunk(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar=None, a
     XR, coef, cell, cw = (X, None, None, None) if nd else (saved[k] for k in ("XR", "coef", "cell", "cw"))
     dev = X.device
     pv = plan.pack_view
-    SP0 = 1 + cfg.S1
+    SP0, split0, need_wgrad = call.SP0, call.split0, dw_flat is not None
     # adjoint of the fc5 output rows (overwrites the forward's out_pre buffer)
     if nd:
         with _timed("reduce_nd_bwd"):
@@ -686,54 +771,50 @@ def _backward_chunk(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar=None, a
                                             jets_bar.shape[2], ptr(saved["roww"]), ptr(bufs[5]), st))
     else:
         with _timed("reduce_bwd"):
-            check(L.stpde_lig_reduce_bwd(C.byref(meta.cfg_out), S, Pc, plan.cout, C.c_void_p(jets_bar.data_ptr() + 4 * p0),
+            check(L.stpde_lig_reduce_bwd(C.byref(call.cfg_out), S, Pc, plan.cout, C.c_void_p(jets_bar.data_ptr() + 4 * p0),
                                          jets_bar.shape[2], ptr(coef), ptr(bufs[5]), st))
     # layer-0 adjoint: the value stream as fragment blocks; the three tangent streams only as per-tile row sums (their
     # layer-0 "input" is the constant column W0[:, d], so only sum_rows matters): 32 + 6 KB per tile instead of 128 KB
     MT0 = plan.layers[0]["MT"]
-    split0 = SP0 == 4 and tan0_rowsum
     z0 = saved["z0"]
     # the value-stream-only layer-0 adjoint goes over the z0 stash (same shape; each lane reads before it writes)
     abar0 = z0 if (split0 or SP0 == 1) else torch.empty(nt * SP0 * MT0 * _FRAG, device=dev)
-    if meta.packed_mask & 1:       # bf16 mode: packed ADJOINT buffer (bf16 blocks) of its own
-        abar0 = torch.empty(_adj_floats(meta, 0, nt), device=dev)
+    if call.packed_mask & 1:       # bf16 mode: packed ADJOINT buffer (bf16 blocks) of its own
+        abar0 = torch.empty(_adj_floats(call, 0, nt), device=dev)
     tan0 = torch.empty(nt * MT0 * 48, device=dev) if split0 else None
     # fc5 -> fc4 -> fc3 input gradients in one kernel (adjoints of layers 4 and 3 feed the next GEMM from the registers).
     # Order: wgrad_5 (needs the pre-activations of fc4's output intact), the chain (abar4 in place; abar3 / abar2 into
     # fresh buffers because wgrad_4 / wgrad_3 still need the pre-activations they would overwrite), wgrad_4, wgrad_3.
-    tail = (fused_tail and plan.nf in (16, 32) and (cfg.S1, cfg.S2) in TAIL_SETS
-            and (cfg.S2 != 1 or cw is not None))
     abar = {l: bufs[l] for l in range(1, 6)}      # where the adjoint of layer l's output rows lives once it exists
-    if meta.packed_mask:           # packed ADJOINT buffers are a format of their own: none of them goes over a stash
-        abar[1], abar[4] = (torch.empty(_adj_floats(meta, k, nt), device=dev) for k in (1, 4))
+    if call.packed_mask:           # packed ADJOINT buffers are a format of their own: none of them goes over a stash
+        abar[1], abar[4] = (torch.empty(_adj_floats(call, k, nt), device=dev) for k in (1, 4))
     for l in range(5, 0, -1):
         lay = plan.layers[l]
-        w16 = meta.packs16.get((l, "WhT")) if meta.packs16 else None
-        d = _layer_desc(nt, lay, cfg, l == 1, meta.nsplit if w16 is not None else 0, _pk(meta, l, l - 1))
+        w16 = packs16.get((l, "WhT")) if packs16 else None
+        d = _layer_desc(call, nt, lay, cfg, l == 1, call.nsplit if w16 is not None else 0, _pk(call, l, l - 1))
         # weight gradient: same operand mode as the layer kernels (``wgrad_split = False`` keeps it on exact-fp32 MFMA in
         # "fp32x3" mode, for A/B timing); only the wide layers, MT >= 8, have bf16-pipe weight-gradient kernels --
         # flagging a narrow layer would take it off its per-wave kernel
-        dwg = _layer_desc(nt, lay, cfg, l == 1, (meta.nsplit if wgrad_split or meta.nsplit == 1 else 0)
-                          if (w16 is not None and lay["MT"] >= 8) else 0, _pk(meta, l, -1) & 5)
-        off, mp, ka = plan.dw_off[l]
-        if (l == 1 and meta.need_wgrad and split0 and w16 is not None and abar0 is not z0
-                and fc1_fused_enabled() and L.stpde_jet_fc1_bwd_supported(C.byref(d))):
+        dwg = _layer_desc(call, nt, lay, cfg, l == 1, (call.nsplit if call.wgrad_split or call.nsplit == 1 else 0)
+                          if (w16 is not None and lay["MT"] >= 8) else 0, _pk(call, l, -1) & 5)
+        if (l == 1 and need_wgrad and split0 and w16 is not None and abar0 is not z0
+                and call.fc1_fused and L.stpde_jet_fc1_bwd_supported(C.byref(d))):
             # bf16 mode, reference width (round 5): weight gradient + input gradient of the first hidden layer in ONE kernel
             # (csrc/jet_fc1_bwd.hip: one read of the adjoint tile, one activation-jet evaluation per z0 element)
             with _timed("layer1_bwd"):
                 check(L.stpde_jet_fc1_bwd(C.byref(d), ptr(abar[1]), ptr(w16), ptr(z0), ptr(pv(packs, 0, "tanc")), ptr(cw),
-                                          ptr(XR), ptr(abar0), ptr(tan0), ptr(dw_flat[_AW() * off:_AW() * (off + mp * ka)]), ptr(pbar), st))
+                                          ptr(XR), ptr(abar0), ptr(tan0), ptr(_dw_slice(call, dw_flat, 1)), ptr(pbar), st))
             continue
-        if meta.need_wgrad:
+        if need_wgrad:
             with _timed("layer%d_wgrad" % l):
                 check(L.stpde_jet_wgrad(C.byref(dwg), S, ptr(abar[l]), ptr(bufs[l - 1]) if l > 1 else ptr(saved["z0"]),
-                                        ptr(XR), ptr(pv(packs, 0, "tanc")), ptr(dw_flat[_AW() * off:_AW() * (off + mp * ka)]), ptr(cw), st))
-        if tail and l >= 3:
+                                        ptr(XR), ptr(pv(packs, 0, "tanc")), ptr(_dw_slice(call, dw_flat, l)), ptr(cw), st))
+        if call.tail and l >= 3:
             if l == 5:
-                abar[3], abar[2] = (torch.empty(_adj_floats(meta, k, nt), device=dev) for k in (3, 2))
+                abar[3], abar[2] = (torch.empty(_adj_floats(call, k, nt), device=dev) for k in (3, 2))
                 arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
-                pk_tail = (meta.packed_mask >> 2) & 1
-                w16s = (C.c_void_p * 3)(meta.packs16[(3, "WhT")].data_ptr(), meta.packs16[(4, "WhT")].data_ptr(), None) \
+                pk_tail = (call.packed_mask >> 2) & 1
+                w16s = (C.c_void_p * 3)(packs16[(3, "WhT")].data_ptr(), packs16[(4, "WhT")].data_ptr(), None) \
                     if pk_tail else None
                 with _timed("tail_dgrad"):
                     check(L.stpde_jet_tail_bwd_p(C.byref(cfg), nt, plan.nf // 16, ptr(bufs[5]),
@@ -751,69 +832,54 @@ def _backward_chunk(meta, packs, saved, jets_bar, dw_flat, dlatent, pbar=None, a
                                         ptr(bufs[l - 1]) if l > 1 else None, ptr(X), ptr(pv(packs, 0, "Ws")),
                                         ptr(pv(packs, 0, "tanc")), ptr(abar0), ptr(cw), ptr(pbar), ptr(w16),
                                         ptr(tan0) if l == 1 else None, ptr(z0) if l == 1 else None, st))
-    if meta.need_wgrad:
+    if need_wgrad:
         lay = plan.layers[0]
         # (bf16 mode: the adjoint is a packed ADJOINT buffer and the contraction over the rows runs on the bf16 MFMA)
-        d = _layer_desc(nt, lay, cfg, False, meta.packed_mask & 1, _pk(meta, 0, -1) & 4)
-        off, mp, ka = plan.dw_off[0]
+        d = _layer_desc(call, nt, lay, cfg, False, call.packed_mask & 1, _pk(call, 0, -1) & 4)
+        dw0 = _dw_slice(call, dw_flat, 0)
         with _timed("layer0_wgrad"):
             if split0:
-                d.cfg = meta.cfg_val      # value stream x raw input (the S = 1 weight-gradient kernels)
-                check(L.stpde_jet_wgrad(C.byref(d), 1, ptr(abar0), None, ptr(XR), None,
-                                        ptr(dw_flat[_AW() * off:_AW() * (off + mp * ka)]), None, st))
-                check(L.stpde_jet_tan0_reduce(nt, MT0, ptr(tan0), ptr(dw_flat[_AW() * off:_AW() * (off + mp * ka)]), ka,
-                                              int(_lib.deterministic), st))
+                d.cfg = call.cfg_val      # value stream x raw input (the S = 1 weight-gradient kernels)
+                check(L.stpde_jet_wgrad(C.byref(d), 1, ptr(abar0), None, ptr(XR), None, ptr(dw0), None, st))
+                check(L.stpde_jet_tan0_reduce(nt, MT0, ptr(tan0), ptr(dw0), plan.dw_off[0][2], int(call.det), st))
             else:
-                check(L.stpde_jet_wgrad(C.byref(d), SP0, ptr(abar0), None, ptr(XR), None,
-                                        ptr(dw_flat[_AW() * off:_AW() * (off + mp * ka)]), ptr(cw), st))
+                check(L.stpde_jet_wgrad(C.byref(d), SP0, ptr(abar0), None, ptr(XR), None, ptr(dw0), ptr(cw), st))
     if dlatent is not None:
         xd = XbarDesc()
         xd.ntiles, xd.nlayers, xd.C = nt, 5, plan.cin
-        xd.n1, xd.n2 = (1, 1) if nd else meta.grid_shape[1:3]      # (read by the atomic scatter only)
+        xd.n1, xd.n2 = (1, 1) if nd else call.grid_shape[1:3]      # (read by the atomic scatter only)
         ab = (C.c_void_p * 5)()
         wt = (C.c_void_p * 5)()
         for l in range(5):
             xd.MT[l] = plan.layers[l]["MT"]
             xd.SP[l] = (1 if split0 else SP0) if l == 0 else S
-            xd.packed[l], xd.S[l] = (meta.packed_mask >> l) & 1, (S if l else 1)
+            xd.packed[l], xd.S[l] = (call.packed_mask >> l) & 1, (S if l else 1)
             ab[l] = (abar0 if l == 0 else abar[l]).data_ptr()
             wt[l] = pv(packs, l, "WsL").data_ptr()
         if nd:
             # per-row adjoints for all 16 * nt rows (k_xbar writes the padding rows of the last tiles too), the cell id of
             # every point, then the per-node sum over 2^dim corners in fixed order
-            cp = (plan.cin + 3) // 4 * 4
-            xrows = torch.empty(16 * nt * cp, device=dev)
-            n_nodes = meta.B * int(np.prod(meta.grid_shape))
+            xrows, perm, start, tmp, n_nodes = _dlatent_scratch(call, 16 * nt, Pc, dev)
             cell = torch.empty(Pc, device=dev, dtype=torch.int32)
-            perm = torch.empty(Pc, device=dev, dtype=torch.int32)
-            start = torch.empty(n_nodes + 1, device=dev, dtype=torch.int32)
-            nb = int(L.stpde_lig_sort_tmp_bytes(Pc, n_nodes))
-            tmp = torch.empty(nb, device=dev, dtype=torch.uint8)
-            gd = _gather_nd_desc(meta, dlatent, Pc, p0, nt)
+            gd = _gather_nd_desc(call, dlatent, Pc, p0, nt)
             with _timed("xbar_scatter"):
                 check(L.stpde_lig_xbar_rows(C.byref(xd), ab, wt, ptr(xrows), st))
                 check(L.stpde_lig_cell_nd(C.byref(gd), ptr(saved["pts_c"]), ptr(cell), st))
-                check(L.stpde_lig_cell_sort(Pc, n_nodes, ptr(cell), ptr(perm), ptr(start), ptr(tmp), nb, st))
-                check(L.stpde_lig_dlatent_reduce_nd(plan.dim, meta.B, (C.c_int * 4)(*meta.grid_shape), plan.cin, ptr(xrows),
+                check(L.stpde_lig_cell_sort(Pc, n_nodes, ptr(cell), ptr(perm), ptr(start), ptr(tmp), tmp.numel(), st))
+                check(L.stpde_lig_dlatent_reduce_nd(plan.dim, call.B, (C.c_int * 4)(*call.grid_shape), plan.cin, ptr(xrows),
                                                     ptr(perm), ptr(start), ptr(dlatent), st))
-        elif not deterministic_dlatent:
+        elif not call.det_dlatent:
             with _timed("xbar_scatter"):
                 check(L.stpde_lig_xbar_scatter(C.byref(xd), ab, wt, ptr(cell), ptr(dlatent), st))
         else:
             # deterministic scatter: per-row adjoints, then a per-node gather in fixed order over the cell-sorted points
             # (the same three library calls the one-call path makes, scratch allocated OUTSIDE the timed region: with torch.sort /
             # index_add_ / cumsum in here the caching allocator's stalls showed up as a 60-75 ms "kernel" in bench.py's table)
-            cp = (plan.cin + 3) // 4 * 4
-            xrows = torch.empty(Pc * 8 * cp, device=dev)
-            n_nodes = meta.B * meta.grid_shape[0] * meta.grid_shape[1] * meta.grid_shape[2]
-            perm = torch.empty(Pc, device=dev, dtype=torch.int32)
-            start = torch.empty(n_nodes + 1, device=dev, dtype=torch.int32)
-            nb = int(L.stpde_lig_sort_tmp_bytes(Pc, n_nodes))
-            tmp = torch.empty(nb, device=dev, dtype=torch.uint8)
+            xrows, perm, start, tmp, n_nodes = _dlatent_scratch(call, Pc * 8, Pc, dev)
             with _timed("xbar_scatter"):
                 check(L.stpde_lig_xbar_rows(C.byref(xd), ab, wt, ptr(xrows), st))
-                check(L.stpde_lig_cell_sort(Pc, n_nodes, ptr(cell), ptr(perm), ptr(start), ptr(tmp), nb, st))
-                check(L.stpde_lig_dlatent_reduce(meta.B, meta.grid_shape[0], meta.grid_shape[1], meta.grid_shape[2],
+                check(L.stpde_lig_cell_sort(Pc, n_nodes, ptr(cell), ptr(perm), ptr(start), ptr(tmp), tmp.numel(), st))
+                check(L.stpde_lig_dlatent_reduce(call.B, call.grid_shape[0], call.grid_shape[1], call.grid_shape[2],
                                                  plan.cin, ptr(xrows), ptr(perm), ptr(start), ptr(dlatent), st))
     if after_dlatent is not None:      # per-kernel (profiling) path: weight gradients first, nothing left to overlap
         after_dlatent()
@@ -830,9 +896,9 @@ sync_hooks = None
 # step near the limit failed with an out-of-memory error in the backward instead of shrinking its chunks).
 expect_two_phase = False
 
-def _chunk_ranges(meta, P):
-    """[(first point, points)] of the launch chunks: ``meta.chunk`` points each."""
-    return [(p0, min(meta.chunk, P - p0)) for p0 in range(0, P, meta.chunk)]
+def _chunk_ranges(call, P):
+    """[(first point, points)] of the launch chunks: ``call.chunk`` points each."""
+    return [(p0, min(call.chunk, P - p0)) for p0 in range(0, P, call.chunk)]
 
 stats = {"recompute_steps": 0}     # calls whose backward rebuilt the stash chunk by chunk (memory plan below)
 
@@ -843,34 +909,34 @@ def _free_bytes(device):
     return free + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
 
 
-def _per_point_bytes(meta):
+def _per_point_bytes(call):
     """(forward stash, backward scratch) bytes per query point of the jet path, from the SAME size functions the chunk
     allocators use (``_buf_floats`` / ``_adj_floats``: fp32 blocks or the packed formats of the bf16 mode), plus the
     fragment images of the augmented input (X, XR), the interpolation coefficients, the per-row weights of a combined
     second-order stream and the cell index.  A point owns 8 of a tile's 16 rows (tile = 2 points); on a dim = 1, 2, 4 grid
     2^dim of them, i.e. 2^dim / 16 tiles, and the per-point extras are the row weights, the cell id and the sort scratch
     (the up to 3 + 1 padding tiles of a chunk, ``nd_tiles``, are not counted: the plan keeps 15 % of headroom)."""
-    plan = meta.plan
+    plan = call.plan
     mt0 = plan.layers[0]["MT"]
     cp = (plan.cin + 3) // 4 * 4
     rows = 8 if plan.dim == 3 else 1 << plan.dim
-    fwd_tile = 4 * (sum(_buf_floats(meta, l, 1) for l in range(1, 6)) + mt0 * _FRAG + XT * _FRAG)
-    bwd_tile = 4 * (_adj_floats(meta, 2, 1) + _adj_floats(meta, 3, 1) + mt0 * 48)
-    if meta.packed_mask:
-        bwd_tile += 4 * (_adj_floats(meta, 1, 1) + _adj_floats(meta, 4, 1) + _adj_floats(meta, 0, 1))
+    fwd_tile = 4 * (sum(_buf_floats(call, l, 1) for l in range(1, 6)) + mt0 * _FRAG + XT * _FRAG)
+    bwd_tile = 4 * (_adj_floats(call, 2, 1) + _adj_floats(call, 3, 1) + mt0 * 48)
+    if call.packed_mask:
+        bwd_tile += 4 * (_adj_floats(call, 1, 1) + _adj_floats(call, 4, 1) + _adj_floats(call, 0, 1))
     if plan.dim != 3:
         fwd = fwd_tile * rows // 16 + 4 * rows                     # + the corner weight of every row
         bwd = bwd_tile * rows // 16 + rows * cp * 4 + 4 + 4 + 24   # per-row latent adjoints, cell id, permutation, sort scratch
         return fwd, bwd
-    fwd = fwd_tile // 2 + 4 * 16 + (4 * 8 if meta.cfg_out.combo else 0) + 4
+    fwd = fwd_tile // 2 + 4 * 16 + (4 * 8 if call.cfg_out.combo else 0) + 4
     bwd = bwd_tile // 2 + 8 * cp * 4 + 4 + 24          # per-row latent adjoints, permutation, radix-sort scratch
     return fwd, bwd
 
 
-def _two_phase_bytes(meta):
+def _two_phase_bytes(call):
     """extra bytes per point of the dgrad-first order (last chunk of a sharded_step backward): two more adjoint buffers"""
-    mt0 = meta.plan.layers[0]["MT"]
-    return 2 * ((0 if meta.packed_mask else _buf_floats(meta, 1, 1)) + (0 if meta.packed_mask & 1 else mt0 * _FRAG))
+    mt0 = call.plan.layers[0]["MT"]
+    return 2 * ((0 if call.packed_mask else _buf_floats(call, 1, 1)) + (0 if call.packed_mask & 1 else mt0 * _FRAG))
 
 
 # Device-memory budget of ONE jet call in bytes (None = whatever the device has free): a call whose forward stash + backward
@@ -888,42 +954,40 @@ def set_memory_budget(nbytes):
     return prev
 
 
-def _avail_bytes(meta, device):
+def _avail_bytes(call, device):
     free = _free_bytes(device)
-    return free if meta.budget is None else min(free, meta.budget)
+    return free if call.budget is None else min(free, call.budget)
 
 
-def _stash_bytes(meta, P):
-    fwd, bwd = _per_point_bytes(meta)
-    last = _chunk_ranges(meta, P)[-1][1]
+def _stash_bytes(call, P):
+    fwd, bwd = _per_point_bytes(call)
+    last = _chunk_ranges(call, P)[-1][1]
     # (the dgrad-first scratch of the last chunk only when the point-sharded step's hooks are / will be installed: ADVICE r4, r5)
-    two = _two_phase_bytes(meta) if (sync_hooks or expect_two_phase) else 0
-    return P * fwd + min(P, meta.chunk) * bwd + last * two
+    two = _two_phase_bytes(call) if (sync_hooks or expect_two_phase) else 0
+    return P * fwd + min(P, call.chunk) * bwd + last * two
 
 
-def _recompute_chunk(meta, device):
+def _recompute_chunk(call, device):
     """Largest power-of-two chunk whose stash + backward scratch takes at most half of the available memory."""
-    fwd, bwd = _per_point_bytes(meta)
-    two = _two_phase_bytes(meta) if (sync_hooks or expect_two_phase) else 0
-    n = max(1, int(0.5 * _avail_bytes(meta, device) / (fwd + bwd + two)))
+    fwd, bwd = _per_point_bytes(call)
+    two = _two_phase_bytes(call) if (sync_hooks or expect_two_phase) else 0
+    n = max(1, int(0.5 * _avail_bytes(call, device) / (fwd + bwd + two)))
     c = 1 << (n.bit_length() - 1)
-    mult = 8 if meta.S == 1 else 2
-    if meta.plan.dim != 3:
+    if call.plan.dim != 3:
         # whole value-tile passes (4 row tiles of 16 >> dim points), and at most the row tiles of the dim = 3 default chunk
-        mult = 4 * (16 >> meta.plan.dim)
-        return max(mult, min(c, (DEFAULT_CHUNK // 2) * (16 >> meta.plan.dim)))
-    return max(mult, min(c, DEFAULT_CHUNK))
+        return max(call.mult, min(c, (DEFAULT_CHUNK // 2) * (16 >> call.plan.dim)))
+    return max(call.mult, min(c, DEFAULT_CHUNK))
 
 
-def _nd_chunk_points(meta, dim, device):
+def _nd_chunk_points(call, device):
     """Default launch chunk of a value-only query on a dim-d grid (dim = 1, 2, 4), in points: the row tiles of the dim = 3
     default chunk, cut down (to a power of two) until one chunk's buffers -- X, the five layer buffers, the row weights --
     take at most half of the call's memory budget / of the free device memory."""
-    tile_bytes = 4 * (sum(_buf_floats(meta, l, 1) for l in range(1, 6)) + XT * _FRAG + 16)
+    tile_bytes = 4 * (sum(_buf_floats(call, l, 1) for l in range(1, 6)) + XT * _FRAG + 16)
     tiles = DEFAULT_CHUNK // 2
-    fit = max(4, int(0.5 * _avail_bytes(meta, device) / tile_bytes))
+    fit = max(4, int(0.5 * _avail_bytes(call, device) / tile_bytes))
     tiles = min(tiles, 1 << (fit.bit_length() - 1))
-    return tiles * (16 >> dim)
+    return max(call.mult, tiles * (16 >> call.plan.dim) // call.mult * call.mult)
 
 
 class LigJetFunction(torch.autograd.Function):
@@ -939,41 +1003,38 @@ class LigJetFunction(torch.autograd.Function):
 
     @staticmethod
     @_lib.guarded
-    def forward(ctx, meta, latent, pts, act_param, *params):
+    def forward(ctx, call, latent, pts, act_param, *params):
         # act_param: the learnable swish beta (a tensor input so that autograd routes its gradient) or None
-        packs = meta.plan.pack(params)
-        meta.packs16 = meta.plan.pack_bf16(packs, meta.nsplit) if meta.bf16 else None
+        packs = call.plan.pack(params)
+        packs16 = call.plan.pack_bf16(packs, call.nsplit) if call.bf16 else None
         P = pts.shape[0]
-        jets = torch.empty(meta.S_out, meta.plan.cout, P, device=pts.device)
+        jets = torch.empty(call.S_out, call.plan.cout, P, device=pts.device)
         # grad mode is always off inside Function.forward and ctx.needs_input_grad ignores torch.no_grad(): whether a
         # backward can follow was decided by lig_jets() before apply()
-        need_grad = meta.need_grad and any(ctx.needs_input_grad)
-        chunk = meta.chunk
+        need_grad = call.need_grad and any(ctx.needs_input_grad)
         # Memory plan (VERDICT r2 #9 / ADVICE r2): the activation stash of ALL chunks lives until the backward.  When it
         # would not fit the free device memory (or an allocation fails half way), the forward keeps NO stash and the
         # backward re-runs the forward kernels chunk by chunk right before each chunk's backward (the same kernels on the
-        # same inputs rebuild the same stash bit for bit): +1 forward of compute, memory bounded by one chunk.
-        limit = 0.85 * _avail_bytes(meta, pts.device)
-        if need_grad and not meta.recompute and _stash_bytes(meta, P) > limit:
+        # same inputs rebuild the same stash bit for bit -- the same kernels because the rebuild reads the SAME frozen record):
+        # +1 forward of compute, memory bounded by one chunk.
+        limit = 0.85 * _avail_bytes(call, pts.device)
+        if need_grad and not call.recompute and _stash_bytes(call, P) > limit:
             # the stash of all chunks is what it is, the backward scratch is per launch chunk: smaller chunks (down to 2^16
             # points: below that the launches get short) before giving up the stash (configs[4], S = 10 at 2^20 points: 187 GB
             # of stash + 69 GB of scratch per 2^20-point chunk, 17 GB per 2^18-point chunk)
-            c = chunk
-            while c > (1 << 16) and _stash_bytes(meta, P) > limit:
-                c //= 2
-                meta.chunk = c
-            if _stash_bytes(meta, P) <= limit:
-                chunk = c
-            else:
-                meta.chunk = chunk
-        recompute = need_grad and (meta.recompute or _stash_bytes(meta, P) > limit)
+            asked = call.chunk
+            while call.chunk > (1 << 16) and _stash_bytes(call, P) > limit:
+                call.plan_chunk(call.chunk // 2)
+            if _stash_bytes(call, P) > limit:
+                call.plan_chunk(asked)
+        recompute = need_grad and (call.recompute or _stash_bytes(call, P) > limit)
         if recompute:
-            chunk = meta.chunk = min(chunk, _recompute_chunk(meta, pts.device))
+            call.plan_chunk(min(call.chunk, _recompute_chunk(call, pts.device)))
         saved = []
         oom = False
         try:
-            for p0, n in _chunk_ranges(meta, P):
-                s = _forward_chunk(meta, packs, latent, pts[p0:p0 + n], jets, p0, need_grad and not recompute)
+            for p0, n in _chunk_ranges(call, P):
+                s = _forward_chunk(call, packs, packs16, latent, pts[p0:p0 + n], jets, p0, need_grad and not recompute)
                 if need_grad and not recompute:
                     saved.append(s)
         except torch.OutOfMemoryError:
@@ -989,12 +1050,12 @@ class LigJetFunction(torch.autograd.Function):
             gc.collect()
             torch.cuda.empty_cache()
             recompute = True
-            chunk = meta.chunk = min(chunk, _recompute_chunk(meta, pts.device))
-            for p0, n in _chunk_ranges(meta, P):
-                _forward_chunk(meta, packs, latent, pts[p0:p0 + n], jets, p0, False)
+            call.plan_chunk(min(call.chunk, _recompute_chunk(call, pts.device)))
+            for p0, n in _chunk_ranges(call, P):
+                _forward_chunk(call, packs, packs16, latent, pts[p0:p0 + n], jets, p0, False)
         stats["recompute_steps"] += int(recompute)
         ctx.recompute = recompute
-        ctx.meta, ctx.packs, ctx.saved = meta, packs, saved
+        ctx.call, ctx.packs, ctx.packs16, ctx.saved = call, packs, packs16, saved
         ctx.inputs = (latent, pts) if need_grad else None   # to rebuild the stash if backward runs again (retain_graph)
         ctx.n_params = len(params)
         ctx.prm_shape = act_param.shape if act_param is not None else None
@@ -1006,7 +1067,7 @@ class LigJetFunction(torch.autograd.Function):
     @staticmethod
     @_lib.guarded
     def backward(ctx, jets_bar):
-        meta = ctx.meta
+        call = ctx.call
         rebuild = ctx.used
         if rebuild and ctx.inputs is None:
             raise RuntimeError("LigJetFunction.backward: no stash was kept for this call")
@@ -1016,11 +1077,10 @@ class LigJetFunction(torch.autograd.Function):
         ctx.used = True
         jets_bar = jets_bar.contiguous()
         dev = jets_bar.device
-        meta.need_wgrad = any(ctx.needs_input_grad[4:])
+        need_wgrad = any(ctx.needs_input_grad[4:])
         need_lat = ctx.needs_input_grad[1]
         # (deterministic mode: long accumulators -- order-independent integer sums -- turned into fp32 after the last chunk)
-        dw_flat = torch.zeros(_AW() * meta.plan.n_dw, device=dev) if meta.need_wgrad else None
-        det_dw = bool(_lib.deterministic) and meta.need_wgrad
+        dw_flat = torch.zeros(_AW(call) * call.plan.n_dw, device=dev) if need_wgrad else None
         dlatent = torch.zeros(ctx.lat_shape, device=dev) if need_lat else None
         pbar = torch.zeros(_lib.PBAR_SLOTS, device=dev) if ctx.needs_input_grad[3] else None
         # Point-sharded multi-GPU step (train_step.sharded_step sets ``sync_hooks``): the all-reduce of the partial d latent is
@@ -1034,29 +1094,26 @@ class LigJetFunction(torch.autograd.Function):
                 works.append(hooks["dlatent"](dlatent))
                 hooks["dlatent_done"] = dlatent      # WHICH tensor is summed over ranks (train_step._SumGradAcrossRanks)
 
+        chunks = ctx.saved
         if rebuild:
             latent, pts = ctx.inputs
-            scratch = torch.empty(meta.S_out, meta.plan.cout, pts.shape[0], device=pts.device)
-            ranges = _chunk_ranges(meta, pts.shape[0])
-            for p0, n in ranges:
-                last = hooks and p0 == ranges[-1][0]
-                s = _forward_chunk(meta, ctx.packs, latent, pts[p0:p0 + n], scratch, p0, True)
-                _backward_chunk(meta, ctx.packs, s, jets_bar, dw_flat, dlatent, pbar, start_dlatent_sync if last else None)
-                s = None
-        else:
-            for k, s in enumerate(ctx.saved):
-                last = hooks and k == len(ctx.saved) - 1
-                _backward_chunk(meta, ctx.packs, s, jets_bar, dw_flat, dlatent, pbar, start_dlatent_sync if last else None)
-                s["bufs"] = s["z0"] = None  # release the stash chunk by chunk
-        ctx.saved = []
+            scratch = torch.empty(call.S_out, call.plan.cout, pts.shape[0], device=pts.device)
+            chunks = _chunk_ranges(call, pts.shape[0])
+        for k, s in enumerate(chunks):
+            if rebuild:     # s = (first point, points): the forward kernels of the chunk, right before its backward
+                s = _forward_chunk(call, ctx.packs, ctx.packs16, latent, pts[s[0]:s[0] + s[1]], scratch, s[0], True)
+            _backward_chunk(call, ctx.packs, ctx.packs16, s, jets_bar, dw_flat, dlatent, pbar,
+                            start_dlatent_sync if (hooks and k == len(chunks) - 1) else None)
+            s["bufs"] = s["z0"] = None  # release the stash chunk by chunk
+        s, ctx.saved = None, []
         grads = [None] * ctx.n_params
-        if det_dw:
-            acc, dw_flat = dw_flat, torch.empty(meta.plan.n_dw, device=dev)
-            check(_lib.lib().stpde_det_finalize(ptr(acc), meta.plan.n_dw, ptr(dw_flat), stream_ptr()))
+        if call.det and need_wgrad:
+            acc, dw_flat = dw_flat, torch.empty(call.plan.n_dw, device=dev)
+            check(_lib.lib().stpde_det_finalize(ptr(acc), call.plan.n_dw, ptr(dw_flat), stream_ptr()))
             del acc
         if hooks:
             hooks["used"] = True
-        if hooks and meta.need_wgrad and hooks.get("dw"):
+        if hooks and need_wgrad and hooks.get("dw"):
             works.append(hooks["dw"](dw_flat))
             if pbar is not None:                      # adjoint of the learnable swish beta: same treatment
                 works.append(hooks["dw"](pbar))
@@ -1064,8 +1121,8 @@ class LigJetFunction(torch.autograd.Function):
         for wk in works:
             if wk is not None:
                 wk.wait()
-        if meta.need_wgrad:
-            g = meta.plan.unpack_grads(dw_flat, ctx.params)
+        if need_wgrad:
+            g = call.plan.unpack_grads(dw_flat, ctx.params)
             grads = [gi if need else None for gi, need in zip(g, ctx.needs_input_grad[4:])]
         dprm = pbar.sum().reshape(ctx.prm_shape) if pbar is not None else None
         return (None, dlatent, None, dprm) + tuple(grads)
@@ -1093,6 +1150,9 @@ def activation_name(module):
 
 # Module-level settings (plain attributes: tests set them with monkeypatch; none of them is read from the environment since
 # round 6 -- the environment selects only the operand mode, the memory budget and the A/B switch of the fused fc1 backward).
+# They are the DEFAULTS of a call: JetCall.make reads each of them (and ``_lib.deterministic``) once, when lig_jets() is called,
+# and every later stage of that call -- its backward and a stash rebuild included -- reads the record.  Setting one between two
+# calls works as ever; setting one between a call's forward and its backward has no effect on that call.
 # d latent: per-node gather in a fixed order (bit-reproducible, like the reference's CPU index_put_ accumulate); False = the
 # fp32-atomic scatter.
 deterministic_dlatent = True
@@ -1112,7 +1172,7 @@ force_recompute = False
 
 def fc1_fused_enabled():
     """bf16 mode: the fused backward of the first hidden layer (csrc/jet_fc1_bwd.hip) is used where the library serves it.
-    STPDE_FC1_FUSED=0 (read per call: tests switch it inside one process) runs the input gradient and the weight gradient of
+    STPDE_FC1_FUSED=0 (read once per call, by JetCall.make: tests switch it inside one process) runs the input gradient and the weight gradient of
     that layer as two kernels -- the A/B reference of tests/test_gpu_bf16_kernel_variants.py."""
     return os.environ.get("STPDE_FC1_FUSED", "1") != "0"
 
@@ -1188,73 +1248,33 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
     plan = ImNetPlan.get(imnet.dim, imnet.in_features, imnet.out_features, imnet.nf)
     if latent_grid.shape[-1] != plan.cin:
         raise ValueError("latent channels != imnet.in_features")
-    meta = _Meta()
-    meta.plan = plan
-    precision = precision or mlp_precision
-    if precision not in ("fp32", "bf16", "fp32x3"):
-        raise ValueError("mlp precision must be 'fp32', 'bf16' or 'fp32x3'")
-    if dim != 3 and precision == "bf16":
-        # (the value-tile kernels have no one-term bf16 variant; local_implicit_grid routes such a query to the composed ops)
-        raise NotImplementedError("dim = %d value queries run with fp32 or fp32x3 operands" % dim)
-    meta.bf16 = precision in ("bf16", "fp32x3")
-    meta.nsplit = 3 if precision == "fp32x3" else 1
-    meta.packs16 = None
-    # bf16 mode, reference width: the stashes of the hidden layers' output rows and their adjoints in the PACKED form -- all
-    # of their consumers are bf16-operand kernels (layers 1-2: k_layer_coop / k_wgrad_coop; fc3 -> fc5: k_tail_fwd_bf /
-    # k_tail_bwd_bf and the bf16 variant of k_wgrad_wave).  STPDE_PACKED_STASH=0: fp32 blocks, fp32 MFMA in fc3 -> fc5.
-    meta.packed_mask = 0
-    # output streams (what the caller gets) vs MLP streams (what the layer kernels carry): for piecewise-linear
-    # activations sigma'' = 0 makes every second-order MLP stream identically zero, so only value + gradient streams
-    # go through the network and the reduction supplies the second derivatives from the weight cross terms
-    meta.cfg_out, meta.S_out, ppairs = make_cfg(act, prm, first, list(pairs), combo)
-    if act in ("relu", "leakyrelu") and ppairs:
-        meta.cfg, meta.S, _ = make_cfg(act, prm, True, [])
-    else:
-        meta.cfg, meta.S = meta.cfg_out, meta.S_out
-    # (S > 6 is not served by the bf16 kernels; the packed buffer of fc2's rows is read by the fused fc3 -> fc5 kernels)
-    if precision == "bf16" and packed_stash and imnet.nf == 32 and meta.S <= 6:
-        tail_ok = fused_tail and meta.cfg.S1 == 3 and (meta.cfg.S2 != 1 or bool(meta.cfg_out.combo))
-        # the buffers of fc1 ... fc4's rows (the bf16 kernels are compiled for "every boundary packed" or none)
-        # bits 1-4: the layer buffers of fc1 ... fc4's rows; bit 0: the value-stream adjoint of layer 0 as bf16 blocks (needs
-        # the tangent row sums: value-only adjoint).  The library serves "all of them" or none.
-        meta.packed_mask = 31 if (tail_ok and tan0_rowsum) else 0
-    meta.B, meta.N = B, N
-    meta.grid_shape = tuple(latent_grid.shape[1:-1])
-    meta.lo_c, meta.hi_c, meta.cube = cached_box_constants(meta.grid_shape, xmin, xmax)
-    meta.need_wgrad = True
-    meta.recompute = force_recompute
-    meta.budget = memory_budget if memory_budget is not None else globals()["memory_budget"]
-    meta.cfg_val = make_cfg(act, prm, False, [])[0]
-    P = B * N
-    if P == 0:   # empty query set: nothing to launch (the reference returns an empty [b, 0, o] tensor as well)
-        return torch.zeros(meta.S_out, plan.cout, 0, device=query_pts.device), ppairs
-    pts = query_pts.detach().reshape(P, dim).contiguous()
-    # tiles hold 2 points; value-only queries are padded to 8 points (4 tiles) for the value-tile kernels
-    mult = 8 if meta.S == 1 else 2
-    if dim != 3:
-        # 16 >> dim points per tile; the gather pads the last tiles of a chunk itself (nd_tiles), the points are not padded.
-        # Default chunk: as many row TILES as the dim = 3 chunk has, so the per-chunk buffers are the same size.
-        mult = 4 * (16 >> dim)
-        chunk_points = chunk_points or _nd_chunk_points(meta, dim, query_pts.device)
-    pad = (-P) % mult if dim == 3 else 0
-    if pad:
-        pts = torch.cat([pts, pts[-1:].expand(pad, 3)], 0)
-    meta.P_pad = P + pad
-    meta.chunk = max(mult, (chunk_points or DEFAULT_CHUNK) // mult * mult)
     lat = latent_grid.contiguous()
     params = []
     for k in range(6):
         params += [imnet.fc[k].weight, imnet.fc[k].bias]
-    meta.need_grad = torch.is_grad_enabled() and (lat.requires_grad or any(p.requires_grad for p in params)
-                                                  or (prm_tensor is not None and prm_tensor.requires_grad))
-    if dim != 3 and meta.need_grad:
-        if not nd_backward:
+    need_grad = torch.is_grad_enabled() and (lat.requires_grad or any(p.requires_grad for p in params)
+                                             or (prm_tensor is not None and prm_tensor.requires_grad))
+    grid_shape = tuple(latent_grid.shape[1:-1])
+    call = JetCall.make(plan, act, prm, first, pairs, combo, precision, grid_shape, cached_box_constants(grid_shape, xmin, xmax),
+                        memory_budget, B, N, chunk_points, need_grad)
+    P = B * N
+    if P == 0:   # empty query set: nothing to launch (the reference returns an empty [b, 0, o] tensor as well)
+        return torch.zeros(call.S_out, plan.cout, 0, device=query_pts.device), call.pairs
+    if dim != 3 and need_grad:
+        if not call.nd_backward:
             raise NotImplementedError("dim = %d queries run in HIP as value-only forward passes: call under torch.no_grad() or "
                                       "without inputs / parameters that require grad" % dim)
         if plan.cin > ND_TRAIN_MAX_CHANNELS:
             raise NotImplementedError("dim = %d training backward in HIP takes in_features <= %d (the latent-adjoint kernel "
                                       "serves two 16-channel tiles)" % (dim, ND_TRAIN_MAX_CHANNELS))
-    jets = LigJetFunction.apply(meta, lat, pts, prm_tensor, *params)
+    if dim != 3 and not chunk_points:
+        # (the default chunk of these grids depends on the device's free memory, which the device-free constructor cannot ask for)
+        call.plan_chunk(_nd_chunk_points(call, query_pts.device))
+    pts = query_pts.detach().reshape(P, dim).contiguous()
+    pad = call.P_pad - P
+    if pad:
+        pts = torch.cat([pts, pts[-1:].expand(pad, 3)], 0)
+    jets = LigJetFunction.apply(call, lat, pts, prm_tensor, *params)
     if pad:
         jets = jets[:, :, :P]
-    return jets, ppairs
+    return jets, call.pairs

@@ -73,18 +73,26 @@ def _pack_indices(co, ci, k, device):
 # runs of the same step give bit-identical outputs, input gradients and parameter gradients, like the reference's CPU path
 # (experiments/rb2d/train.py:77).  Cost: 48 bytes of zero-filled scratch per weight element per step (~450 MB at
 # configs[1]) and one finalize pass; timings in DESIGN 7.
+# The mode is read at FORWARD time only (``_det()``): every autograd node keeps its reading in ``ctx.det``, the U-Net takes one
+# reading per step for the buffers it sizes and hands it to the nodes it serves, and a backward uses what was kept -- the
+# accumulators a kernel writes always have the format their buffer was sized for, whatever the flag says by then.
 def _det():
     return 1 if _lib.deterministic else 0
 
 
-def _acc_zeros(n, device):
+def _acc_w(det):
+    """floats of storage per accumulated element"""
+    return 2 * _lib.DET_K if det else 1
+
+
+def _acc_zeros(n, device, det):
     """zero-filled destination of n accumulated floats: n floats, or -- deterministic mode -- n long accumulators"""
-    return torch.zeros(n * (2 * _lib.DET_K if _lib.deterministic else 1), device=device)
+    return torch.zeros(n * _acc_w(det), device=device)
 
 
-def _acc_value(acc, n):
+def _acc_value(acc, n, det):
     """fp32 values of a destination made by _acc_zeros (deterministic mode: stpde_det_finalize into a fresh tensor)"""
-    if not _lib.deterministic:
+    if not det:
         return acc
     out = torch.empty(n, device=acc.device)
     _lib.check(_lib.lib().stpde_det_finalize(_lib.ptr(acc), n, _lib.ptr(out), _lib.stream_ptr()))
@@ -111,11 +119,12 @@ def _bf16():
     return 1 if conv_precision == "bf16" else 0
 
 
-def _desc(x, ci, co, k, bf=0):
+def _desc(x, ci, co, k, bf=0, det=None):
     d = _lib.Conv3dDesc()
     d.B, d.T, d.Z, d.X = x.shape[0], x.shape[1], x.shape[2], x.shape[3]
     d.Ci, d.Co, d.ksize = ci, co, k
-    d.det = _det()
+    d.det = _det() if det is None else det      # (None: a forward-time caller that takes its own reading; every autograd
+    #                                             node passes the ctx.det of its forward)
     d.mfma_bf16 = bf if k == 3 else 0
     return d
 
@@ -143,14 +152,14 @@ class _DeferredGrads:
     most of the chip idle; the weight-gradient kernels fill it.  Only ``loss.backward()`` sees the gradients (they are
     accumulated into ``.grad``); ``torch.autograd.grad(..., unet.parameters())`` does not -- hence opt-in."""
 
-    def __init__(self, convs, dwall, sizes, device):
+    def __init__(self, convs, dwall, sizes, device, det):
         self.convs, self.dwall, self.device = convs, dwall, device
         self.side = _side_stream(device)
         nb = [c.weight.shape[0] if c.bias is not None else 0 for c in convs]
         self.nbias = max(1, sum(nb))
-        self.dball = _acc_zeros(self.nbias, device)
+        self.dball = _acc_zeros(self.nbias, device, det)
         self.boff = np.concatenate([[0], np.cumsum(nb)]).astype(np.int64)
-        self.acc_w = 2 * _lib.DET_K if _lib.deterministic else 1      # floats of storage per accumulated element
+        self.acc_w = _acc_w(det)     # (the step's reading of the mode, as dwall was sized: UNet3d._prepare_step)
         self.used = set()
         self.keep = []
         self.direct_bias = {}        # bias gradients that did not come out of a weight-gradient kernel (frozen weights)
@@ -186,8 +195,8 @@ class _DeferredGrads:
             torch.cuda.current_stream().wait_stream(self.side)
             self.keep = []                           # operands of the side-stream kernels: free for reuse on this stream now
             if self.acc_w != 1:                      # deterministic mode: long accumulators -> fp32, then as usual
-                self.dwall = _acc_value(self.dwall, self.dwall.numel() // self.acc_w)
-                self.dball = _acc_value(self.dball, self.nbias)
+                self.dwall = _acc_value(self.dwall, self.dwall.numel() // self.acc_w, 1)
+                self.dball = _acc_value(self.dball, self.nbias, 1)
                 self.acc_w = 1
             gflat = self.dwall[self.uidx]            # one gather: every weight gradient in parameter layout
             o = 0
@@ -220,13 +229,14 @@ class _Conv3dHip(torch.autograd.Function):
             raise NotImplementedError("HIP conv3d needs out_channels to be a multiple of 16 (got %d)" % co)
         ctx.dwbuf = ctx.defer = None
         if packs is None:
+            ctx.det = _det()                    # deterministic mode of this node: its backward uses the same
             fidx, bidx, _, _ = _pack_indices(co, ci, k, x.device)
             wflat = torch.cat([weight.detach().reshape(-1), weight.new_zeros(1)])
             fpack, bpack = wflat[fidx], None
         else:
-            fpack, bpack, ctx.dwbuf = packs[:3]
-            if len(packs) > 3:
-                ctx.defer = packs[3:5]              # (_DeferredGrads, index of this convolution in it)
+            fpack, bpack, ctx.dwbuf, ctx.det = packs[:4]      # (the mode: the step's reading, as dwbuf was sized)
+            if len(packs) > 4:
+                ctx.defer = packs[4:6]              # (_DeferredGrads, index of this convolution in it)
             wflat = bidx = None
         xin = x.detach()
         if cip != ci:
@@ -234,7 +244,7 @@ class _Conv3dHip(torch.autograd.Function):
         xin = xin.contiguous()
         y = torch.empty(x.shape[:-1] + (co,), device=x.device, dtype=torch.float32)
         ctx.bf = _bf16() if k == 3 else 0       # operand mode of this node: its backward uses the same
-        d = _desc(xin, cip, co, k, ctx.bf)
+        d = _desc(xin, cip, co, k, ctx.bf, ctx.det)
         _lib.check(L.stpde_conv3d_fwd(C.byref(d), _lib.ptr(xin), _lib.ptr(fpack),
                                       _lib.ptr(bias.detach().contiguous()) if bias is not None else None,
                                       _lib.ptr(y), _lib.stream_ptr()))
@@ -254,7 +264,7 @@ class _Conv3dHip(torch.autograd.Function):
         ready = torch.cuda.current_stream().record_event() if ctx.defer is not None else None   # gy is complete here
         if ctx.needs_input_grad[0]:
             dxp = torch.empty(xin.shape, device=gy.device, dtype=torch.float32)
-            d = _desc(gy, co, cip, k, ctx.bf)
+            d = _desc(gy, co, cip, k, ctx.bf, ctx.det)
             bpack = wsaved if bidx is None else wsaved[bidx]
             _lib.check(L.stpde_conv3d_fwd(C.byref(d), _lib.ptr(gy), _lib.ptr(bpack), None, _lib.ptr(dxp),
                                           _lib.stream_ptr()))
@@ -271,7 +281,7 @@ class _Conv3dHip(torch.autograd.Function):
                 if ctx.needs_input_grad[1]:
                     # (the bias gradient = column sums of gy comes out of the same kernel: dball is zero-filled per step)
                     dwt, ctx.dwbuf = ctx.dwbuf, None
-                    d = _desc(xin, cip, co, k, ctx.bf)
+                    d = _desc(xin, cip, co, k, ctx.bf, ctx.det)
                     _lib.check(L.stpde_conv3d_wgrad_bias(C.byref(d), _lib.ptr(xin), _lib.ptr(gy), _lib.ptr(dwt),
                                                          _lib.ptr(defer.bias_slice(idx)) if want_b else None,
                                                          _lib.stream_ptr()))
@@ -283,15 +293,15 @@ class _Conv3dHip(torch.autograd.Function):
             ntap = k ** 3
             dwt, ctx.dwbuf = ctx.dwbuf, None     # zero-filled slice of the per-step buffer (used once), else a fresh one
             if dwt is None:
-                dwt = _acc_zeros(ntap * co * cip, gy.device)
-            d = _desc(xin, cip, co, k, ctx.bf)
+                dwt = _acc_zeros(ntap * co * cip, gy.device, ctx.det)
+            d = _desc(xin, cip, co, k, ctx.bf, ctx.det)
             if has_bias and ctx.needs_input_grad[2]:
-                db = _acc_zeros(co, gy.device)     # column sums of gy, from the same kernel
+                db = _acc_zeros(co, gy.device, ctx.det)     # column sums of gy, from the same kernel
             _lib.check(L.stpde_conv3d_wgrad_bias(C.byref(d), _lib.ptr(xin), _lib.ptr(gy), _lib.ptr(dwt), _lib.ptr(db),
                                                  _lib.stream_ptr()))
-            dwt = _acc_value(dwt, ntap * co * cip).view(ntap, co, cip)     # (deterministic mode: long accumulators -> fp32)
+            dwt = _acc_value(dwt, ntap * co * cip, ctx.det).view(ntap, co, cip)     # (deterministic mode: long accumulators -> fp32)
             if db is not None:
-                db = _acc_value(db, co)
+                db = _acc_value(db, co, ctx.det)
             dw = dwt[:, :, :ci].permute(1, 2, 0).reshape(co, ci, k, k, k)
         if has_bias and ctx.needs_input_grad[2] and db is None:
             db = gy.reshape(-1, co).sum(0)
@@ -561,12 +571,13 @@ class _ResBlockHip(torch.autograd.Function):
         R = _lib.BN_REP
         convs = (blk.conv1, blk.conv2, blk.conv3, blk.shortcut)
         packs = []
+        det = _det()                          # ONE reading for the convolutions of this node that the step does not serve
         for conv, w in zip(convs, (w1, w2, w3, ws)):
             p = getattr(conv, "_stpde_packs", None)
             if p is None:
                 fidx, bidx, _, _ = _pack_indices(w.shape[0], w.shape[1], w.shape[2], dev)
                 wflat = torch.cat([w.detach().reshape(-1), w.new_zeros(1)])
-                p = (wflat[fidx], wflat[bidx], None)
+                p = (wflat[fidx], wflat[bidx], None, det)
             packs.append(p)
         bns = (blk.bn1, blk.bn2, blk.bn3)
         fsum, bsum, stat = [], [], []
@@ -583,12 +594,14 @@ class _ResBlockHip(torch.autograd.Function):
         rm = [bn.running_mean if bn.track_running_stats else None for bn in bns]
         rv = [bn.running_var if bn.track_running_stats else None for bn in bns]
         ctx.bf = _bf16()                      # operand mode of conv2 (3x3x3), for the forward and the backward of this node
+        ctx.det = packs[0][3]                 # deterministic mode, likewise (the step's reading, or this node's own)
+        assert all(p[3] == ctx.det for p in packs), "one deterministic mode per residual block"
 
         def conv_args(ci_, co_, k):
             a = _lib.Conv3dFusedArgs()
             a.d.B, a.d.T, a.d.Z, a.d.X = shp
             a.d.Ci, a.d.Co, a.d.ksize = ci_, co_, k
-            a.d.det = _det()
+            a.d.det = ctx.det
             a.d.mfma_bf16 = ctx.bf if k == 3 else 0
             return a
 
@@ -596,7 +609,7 @@ class _ResBlockHip(torch.autograd.Function):
             d = _lib.BnDesc()
             d.N, d.C, d.training, d.relu, d.eps, d.momentum = N, c, 1, int(relu), float(bn.eps), float(bn.momentum)
             d.scratch_zeroed, d.stats_mode = 1, 2
-            d.det = _det()
+            d.det = ctx.det
             return d
 
         st = _lib.stream_ptr()
@@ -641,7 +654,7 @@ class _ResBlockHip(torch.autograd.Function):
         ctx.meta = (shp, N, ci, cip, cn, co, bool(blk.final_relu), [float(bn.eps) for bn in bns],
                     [float(bn.momentum) for bn in bns], (b1 is not None, b2 is not None, b3 is not None, bs is not None))
         ctx.bsum = bsum
-        ctx.dw = [(p[2], p[3:5] if len(p) > 3 else None) for p in packs]
+        ctx.dw = [(p[2], p[4:6] if len(p) > 4 else None) for p in packs]
         stats["fused_resblocks"] += 1
         return out
 
@@ -667,7 +680,7 @@ class _ResBlockHip(torch.autograd.Function):
             a = _lib.Conv3dFusedArgs()
             a.d.B, a.d.T, a.d.Z, a.d.X = shp
             a.d.Ci, a.d.Co, a.d.ksize = ci_, co_, k
-            a.d.det = _det()
+            a.d.det = ctx.det
             a.d.mfma_bf16 = ctx.bf if k == 3 else 0
             return a
 
@@ -675,7 +688,7 @@ class _ResBlockHip(torch.autograd.Function):
             d = _lib.BnDesc()
             d.N, d.C, d.training, d.relu, d.eps, d.momentum = N, c, 1, int(relu), eps[k], mom[k]
             d.scratch_zeroed, d.reduce_done = int(zeroed), int(reduce_done)
-            d.det = _det()
+            d.det = ctx.det
             return d
 
         defer = ctx.dw[0][1][0] if ctx.dw[0][1] else None
@@ -746,7 +759,7 @@ class _ResBlockHip(torch.autograd.Function):
             cd = _lib.Conv3dDesc()
             cd.B, cd.T, cd.Z, cd.X = shp
             cd.Ci, cd.Co, cd.ksize = ci_, co_, ks
-            cd.det = _det()
+            cd.det = ctx.det
             cd.mfma_bf16 = ctx.bf if ks == 3 else 0
 
             def launch(dwt, dbt):
@@ -766,12 +779,12 @@ class _ResBlockHip(torch.autograd.Function):
                 dobj.enqueue(idx)
             else:
                 if dwt is None:
-                    dwt = _acc_zeros(ks ** 3 * co_ * ci_, dev)
-                dbt = _acc_zeros(co_, dev) if has_b[k] else None
+                    dwt = _acc_zeros(ks ** 3 * co_ * ci_, dev, ctx.det)
+                dbt = _acc_zeros(co_, dev, ctx.det) if has_b[k] else None
                 launch(dwt, dbt)
-                dwt = _acc_value(dwt, ks ** 3 * co_ * ci_).view(ks ** 3, co_, ci_)     # (deterministic mode: -> fp32)
+                dwt = _acc_value(dwt, ks ** 3 * co_ * ci_, ctx.det).view(ks ** 3, co_, ci_)     # (deterministic mode: -> fp32)
                 if dbt is not None:
-                    dbt = _acc_value(dbt, co_)
+                    dbt = _acc_value(dbt, co_, ctx.det)
                 cin = ci if k in (0, 3) else ci_
                 if ctx.needs_input_grad[2 + 2 * k]:
                     gw[k] = dwt[:, :, :cin].permute(1, 2, 0).reshape(co_, cin, ks, ks, ks)
@@ -940,11 +953,12 @@ class UNet3d(nn.Module):  # pylint: disable=too-many-instance-attributes
         # one zero-filled buffer for all weight gradients of this step (the kernels accumulate with atomics)
         need_dw = torch.is_grad_enabled() and any(c.weight.requires_grad for c in convs)
         sizes = [c.weight.shape[2] ** 3 * c.weight.shape[0] * ((c.weight.shape[1] + 15) // 16 * 16) for c in convs]
-        dwall = _acc_zeros(sum(sizes), device) if need_dw else None
-        aw = 2 * _lib.DET_K if _lib.deterministic else 1          # floats of storage per accumulated element
+        det = _det()             # ONE reading per step: sizes dwall and goes to every node that gets a slice of it
+        dwall = _acc_zeros(sum(sizes), device, det) if need_dw else None
+        aw = _acc_w(det)
         defer = None
         if need_dw and self.deferred_weight_grads:
-            defer = _DeferredGrads(convs, dwall, sizes, device)
+            defer = _DeferredGrads(convs, dwall, sizes, device, det)
             if len(plan) < 4:
                 plan = plan + (_DeferredGrads.unpack_index(convs, sizes, device),)
                 self._pack_plan = plan
@@ -953,7 +967,7 @@ class UNet3d(nn.Module):  # pylint: disable=too-many-instance-attributes
         for i, (c, (a, b, e), n) in enumerate(zip(convs, plan[2], sizes)):
             co, ci, k = c.weight.shape[0], c.weight.shape[1], c.weight.shape[2]
             dw = dwall[aw * o:aw * (o + n)] if need_dw else None      # (flat: the kernels index [tap][co][ci padded] themselves)
-            c._stpde_packs = (packs[a:b], packs[b:e], dw) + ((defer, i) if defer is not None else ())
+            c._stpde_packs = (packs[a:b], packs[b:e], dw, det) + ((defer, i) if defer is not None else ())
             o += n
         bns = []
         if self.training:

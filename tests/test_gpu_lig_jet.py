@@ -477,3 +477,41 @@ def test_bf16_mode_packed_buffers_on_the_side_paths(hiplib, monkeypatch):
     jets, latd, cot = run()
     (jets * cot).sum().backward()
     assert _relerr(latd.grad, g0.double().cpu()) < 5e-6
+
+
+@pytest.mark.parametrize("pipeline", [True, False])
+@pytest.mark.parametrize("recompute", [False, True])
+def test_deterministic_mode_of_a_call_is_the_one_its_forward_saw(hiplib, monkeypatch, recompute, pipeline):
+    """``_lib.deterministic`` is read once, when the call is made (lig_jet.JetCall): switching it off between the forward and
+    the backward changes nothing -- d latent and all twelve parameter gradients are bit-identical to a run with the mode on
+    throughout, with a kept stash and with a stash rebuilt in the backward, through the one-call driver and kernel by kernel.
+    (Only this direction runs on a device: the buffers of the deterministic mode are the larger ones.)"""
+    from space_time_pde_amd import _lib, implicit_net, lig_jet
+    dev = torch.device("cuda:0")
+    torch.manual_seed(11)
+    net = implicit_net.ImNet(dim=3, in_features=8, out_features=4, nf=32).to(dev)
+    g = torch.Generator().manual_seed(12)
+    lat = 0.5 * torch.randn(1, 3, 3, 3, 8, generator=g)
+    pts = (0.02 + 0.96 * torch.rand(1, 16, 3, generator=g)).to(dev)
+    monkeypatch.setattr(lig_jet, "force_recompute", recompute)
+    monkeypatch.setattr(lig_jet, "use_pipeline", pipeline)
+
+    def run(off_before_backward):
+        monkeypatch.setattr(_lib, "deterministic", True)
+        for p in net.parameters():
+            p.grad = None
+        latd = lat.to(dev).requires_grad_(True)
+        n0 = lig_jet.stats["recompute_steps"]
+        jets, _ = lig_jet.lig_jets(net, latd, pts, 0., 1., True, [(1, 1), (2, 2)], chunk_points=8, precision="fp32")
+        assert lig_jet.stats["recompute_steps"] == n0 + int(recompute)
+        cot = torch.randn(jets.shape, generator=torch.Generator().manual_seed(13)).to(dev)
+        if off_before_backward:
+            monkeypatch.setattr(_lib, "deterministic", False)
+        (jets * cot).sum().backward()
+        torch.cuda.synchronize()
+        return [latd.grad.clone()] + [p.grad.clone() for p in net.parameters()]
+
+    ref, got = run(False), run(True)
+    assert len(ref) == 13
+    for k, (a, b) in enumerate(zip(ref, got)):
+        assert a.abs().max().item() > 0 and torch.equal(a, b), k

@@ -235,16 +235,12 @@ def test_fused_clip_adam_survives_deepcopy_and_pickle():
             clone.step()          # no gradients anywhere: nothing to launch, but every attribute step() reads must exist
 
 
-def _plan_meta(packed=0):
-    """A jet-call descriptor as lig_jets() builds it (reference width, RB2 stream set), without any device."""
+def _plan_meta(budget=None):
+    """The record of a jet call as lig_jets() builds it (reference width, RB2 stream set, exact fp32), without any device."""
     from space_time_pde_amd import lig_jet
-    meta = lig_jet._Meta()
-    meta.plan = lig_jet.ImNetPlan.get(3, 32, 4, 32)
-    meta.bf16, meta.nsplit, meta.packs16, meta.packed_mask = bool(packed), 1, None, packed
-    meta.cfg_out, meta.S_out, _ = lig_jet.make_cfg("softplus", 0.0, True, [], {(1, 1): 1.0, (2, 2): 1.0})
-    meta.cfg, meta.S = meta.cfg_out, meta.S_out
-    meta.chunk, meta.tail, meta.budget = 1 << 20, 0, None
-    return meta
+    grid = (4, 8, 8)
+    return lig_jet.JetCall.make(lig_jet.ImNetPlan.get(3, 32, 4, 32), "softplus", 0.0, True, [], {(1, 1): 1.0, (2, 2): 1.0},
+                                "fp32", grid, lig_jet.box_constants(grid, 0., 1.), budget, chunk_points=1 << 20)
 
 
 def test_memory_plan_counts_the_two_phase_scratch_when_the_sharded_step_will_use_it(monkeypatch):
@@ -268,7 +264,7 @@ def test_memory_plan_counts_the_two_phase_scratch_when_the_sharded_step_will_use
     monkeypatch.setattr(lig_jet, "_free_bytes", lambda device: 1 << 60)
     shrunk = 0
     for mib in range(1024, 2049, 64):     # (chunks are powers of two: the term shows at some budgets, never grows the chunk)
-        meta.budget = mib << 20
+        meta = _plan_meta(budget=mib << 20)
         monkeypatch.setattr(lig_jet, "expect_two_phase", False)
         c0 = lig_jet._recompute_chunk(meta, None)
         monkeypatch.setattr(lig_jet, "expect_two_phase", True)

@@ -311,10 +311,10 @@ def test_memory_plan_counts_rows_per_point():
     """stash / scratch bytes per point scale with the 2^d rows a point owns (dim = 3: 8 rows, unchanged)"""
     per = {}
     for dim in (1, 2, 3, 4):
-        meta = lig_jet._Meta()
-        meta.plan = lig_jet.ImNetPlan.get(dim, 8, 3, 16)
-        meta.S, meta.packed_mask = 1, 0
-        meta.cfg_out = lig_jet.make_cfg("softplus", 0.0, False, [])[0]
+        grid = (4,) * dim
+        meta = lig_jet.JetCall.make(lig_jet.ImNetPlan.get(dim, 8, 3, 16), "softplus", 0.0, False, [], None, "fp32", grid,
+                                    lig_jet.box_constants(grid, 0., 1.))
+        assert (meta.S, meta.packed_mask) == (1, 0)
         per[dim] = lig_jet._per_point_bytes(meta)
         rows = 1 << dim
         mt = [lay["MT"] for lay in meta.plan.layers]

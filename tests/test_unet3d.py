@@ -491,6 +491,40 @@ def test_deterministic_mode_unet_backward_is_bit_reproducible(hiplib, monkeypatc
 
 
 @pytest.mark.gpu
+def test_deterministic_mode_of_a_unet_step_is_the_one_its_forward_saw(hiplib, monkeypatch):
+    """Every node keeps the deterministic mode it ran its forward in, and the per-step gradient buffers (deferred weight
+    gradients on) are finalized in the format they were sized for: switching ``_lib.deterministic`` off between the forward and
+    the backward changes no bit of the input gradient or of any parameter gradient.  (Only this direction runs on a device: the
+    buffers of the deterministic mode are the larger ones.)"""
+    from space_time_pde_amd import _lib
+    dev = torch.device("cuda:0")
+    torch.manual_seed(21)
+    net0 = unet3d.UNet3d(in_features=4, out_features=32, igres=(32, 128, 128), nf=16, mf=256).to(dev).train()
+    net0.deferred_weight_grads = True
+    state = {k: v.clone() for k, v in net0.state_dict().items()}
+    g = torch.Generator().manual_seed(22)
+    x0 = torch.randn(1, 4, 32, 128, 128, generator=g).to(dev)
+    cot = torch.randn(1, 32, 32, 128, 128, generator=g).to(dev)
+
+    def run(off_before_backward):
+        monkeypatch.setattr(_lib, "deterministic", True)
+        net0.load_state_dict(state)
+        for p in net0.parameters():
+            p.grad = None
+        x = x0.clone().requires_grad_(True)
+        y = net0(x)
+        if off_before_backward:
+            monkeypatch.setattr(_lib, "deterministic", False)
+        y.backward(cot)
+        torch.cuda.synchronize()
+        return [x.grad.clone()] + [p.grad.clone() for p in net0.parameters()]
+
+    ref, got = run(False), run(True)
+    for k, (a, b) in enumerate(zip(ref, got)):
+        assert torch.equal(a, b), (k, (a - b).abs().max().item())
+
+
+@pytest.mark.gpu
 def test_long_accumulator_finalize_matches_fp64(hiplib):
     """csrc/common.h det_add_f32 / det_value through the public pair (stpde_conv3d_wgrad with det = 1, stpde_det_finalize): a
     1x1x1 weight gradient over 300,000 voxels with values spanning 12 orders of magnitude equals the fp64 sum to fp32 rounding,

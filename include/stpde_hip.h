@@ -763,6 +763,44 @@ int stpde_sampler_produce(const stpde_sampler_desc* d, stpde_sampler_state* stat
                           const stpde_sampler_tap* taps_x, const int* crop_idx, const float* point_coord,
                           float* lres_out, float* point_value_out, void* stream);
 
+/* ---- N3 on the device, with the low-res pre-filter (lres_filter = gaussian / uniform / maximum) --------------------
+ * What RB2DeviceLoader.get() does with dataloader_spacetime.lres_filter before it interpolates (reference
+ * experiments/rb2d/dataloader_spacetime.py:96-116, :136-155), bit for bit, in capturable launches: the high-res crops of the
+ * batch are filtered into a scratch crop, and BOTH outputs are then interpolated from it by the produce entry below.
+ * `median` has no kernel (not separable; a selection over 7 * 15 * 15 values at the reference's sizes).
+ *
+ * The filter acts on the crop [nt][nz][nx] per channel with scipy's 'reflect' boundary at the CROP faces (the edge sample is
+ * repeated, period 2n, any radius); dataset values outside the crop are never read.  Up to three 1-D passes run in the order
+ * t, z, x, each on the fp32 result of the one before; an axis with r = 0 is skipped, not run with one tap.
+ *   gaussian, uniform: out[i] = (((+0 + w[0] x[i-r]) + w[1] x[i-r+1]) + ...) + w[2r] x[i+r], a separate fp32 multiply and add
+ *                      per tap.  The tables are the caller's: w_t, w_z, w_x of 2r + 1 fp32 each (nw = 2r + 1), in device memory.
+ *   maximum:           the largest of the 2r + 1 taps; a NaN tap gives NaN.  No tables (nw = 0, the pointers may be null).
+ * The first pass that runs reads data_cl at the crop origin of crop_idx[b] -- clamped into [0, len) before any address is
+ * formed and counted in state->oob, exactly as the produce entry does; later passes read scratch.  scratch_a and scratch_b are
+ * [B][nt][nz][nx][4] fp32, 16-byte aligned, caller-owned and distinct; the passes ping-pong between them and the result is
+ * ALWAYS left in scratch_a (with no axis to filter, a plain copy of the crops).  Nothing allocates or synchronises. */
+#define STPDE_FILTER_GAUSSIAN 1
+#define STPDE_FILTER_UNIFORM 2
+#define STPDE_FILTER_MAXIMUM 3
+typedef struct {
+  int T, Z, X;           /* dataset extents                                                  */
+  int nt, nz, nx;        /* crop extents (>= 2 each)                                         */
+  int rt, rz, rx;        /* crop ranges: T - nt + 1, Z - nz + 1, X - nx + 1                  */
+  int B;                 /* crops per batch                                                  */
+  int kind;              /* STPDE_FILTER_GAUSSIAN / _UNIFORM / _MAXIMUM                      */
+  int r[3];              /* radius along t, z, x, in [0, 2^20]; 0: the axis is skipped       */
+  int nw[3];             /* entries of w_t, w_z, w_x: 2 r + 1 on a weighted axis that runs, else 0 */
+} stpde_sampler_filter_desc;
+int stpde_sampler_filter(const stpde_sampler_filter_desc* d, stpde_sampler_state* state_dev, const float* data_cl,
+                         const int* crop_idx, const float* w_t, const float* w_z, const float* w_x, float* scratch_a,
+                         float* scratch_b, void* stream);
+/* stpde_sampler_produce on filtered crops: `crops` [B][nt][nz][nx][4] (scratch_a of the entry above) is read with crop-local
+ * addressing, origin 0 of crop b; the crop ids are not looked at again (nothing is counted twice).  Same arithmetic, same
+ * outputs; d is the descriptor the unfiltered entry takes. */
+int stpde_sampler_produce_filtered(const stpde_sampler_desc* d, const float* crops, const stpde_sampler_tap* taps_t,
+                                   const stpde_sampler_tap* taps_z, const stpde_sampler_tap* taps_x, const float* point_coord,
+                                   float* lres_out, float* point_value_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

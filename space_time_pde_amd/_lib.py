@@ -147,6 +147,15 @@ class SamplerDesc(C.Structure):
                 ("std", C.c_float * 4), ("lo_c", C.c_float * 3), ("hi_c", C.c_float * 3), ("cube", C.c_float * 3)]
 
 
+class SamplerFilterDesc(C.Structure):    # stpde_sampler_filter_desc
+    _fields_ = [("T", C.c_int), ("Z", C.c_int), ("X", C.c_int), ("nt", C.c_int), ("nz", C.c_int), ("nx", C.c_int),
+                ("rt", C.c_int), ("rz", C.c_int), ("rx", C.c_int), ("B", C.c_int), ("kind", C.c_int), ("r", C.c_int * 3),
+                ("nw", C.c_int * 3)]
+
+
+FILTER_KINDS = {"gaussian": 1, "uniform": 2, "maximum": 3}     # STPDE_FILTER_*
+
+
 def _sources():
     return [os.path.join(_CSRC, s) for s in _SOURCES if os.path.exists(os.path.join(_CSRC, s))]
 
@@ -291,6 +300,8 @@ _SIGNATURES = {
     "stpde_clip_sgd_multi": ([C.POINTER(SgdDesc), _VP, _VP, _VP, C.c_int, C.c_int, _VP], C.c_int),
     "stpde_sampler_draw": ([C.POINTER(SamplerDesc)] + [_VP] * 4, C.c_int),
     "stpde_sampler_produce": ([C.POINTER(SamplerDesc)] + [_VP] * 10, C.c_int),
+    "stpde_sampler_filter": ([C.POINTER(SamplerFilterDesc)] + [_VP] * 9, C.c_int),
+    "stpde_sampler_produce_filtered": ([C.POINTER(SamplerDesc)] + [_VP] * 8, C.c_int),
 }
 
 

@@ -11,8 +11,8 @@ reference's constructor signature (:18-21) and ``__getitem__`` tuple (:118-171),
 produced by the imported reference loader (tests/golden/n3_dataloader.npz).
 
 ``DeviceBatchSampler`` draws whole training batches of an ``RB2DeviceLoader`` on the device with capturable launches
-(csrc/sampler.hip), bit-identical to ``RB2DeviceLoader.get()`` on the same crop ids and points; ``sampler_expected`` is
-its host model.
+(csrc/sampler.hip), bit-identical to ``RB2DeviceLoader.get()`` on the same crop ids and points -- with
+``filter_on_device=True`` also for the gaussian / uniform / maximum pre-filters; ``sampler_expected`` is its host model.
 """
 import os
 
@@ -52,6 +52,29 @@ def _window_view(x, sizes):
     return v.reshape(v.shape[:-3] + (t * z * xx,))
 
 
+def filter_axis_weights(kind, downsamp_t, downsamp_xz, device, dtype=torch.float32):
+    """The per-axis (t, z, x) correlation weights of the separable pre-filters, ``None`` for an axis the filter skips:
+    gaussian = exp(-k^2 / 2 sigma^2), sigma = int(downsamp / 2), |k| <= int(4 sigma + 0.5), normalised in fp64 and then cast
+    (skipped when sigma <= 0); uniform = 2 downsamp - 1 taps of 1 / size (skipped when the window is 1).  ``lres_filter`` and
+    the device sampler's constructor both take their tables from here."""
+    out = []
+    if kind == 'gaussian':
+        for sigma in (int(downsamp_t / 2), int(downsamp_xz / 2), int(downsamp_xz / 2)):
+            if sigma <= 0:
+                out.append(None)
+                continue
+            r = int(4.0 * sigma + 0.5)
+            k = torch.arange(-r, r + 1, device=device, dtype=torch.float64)
+            w = torch.exp(-0.5 * k * k / (sigma * sigma))
+            out.append((w / w.sum()).to(dtype))
+    elif kind == 'uniform':
+        for sz in (downsamp_t * 2 - 1, downsamp_xz * 2 - 1, downsamp_xz * 2 - 1):
+            out.append(torch.full((sz,), 1.0 / sz, device=device, dtype=dtype) if sz > 1 else None)
+    else:
+        raise ValueError("no weight tables for lres_filter=%r" % (kind,))
+    return out
+
+
 def lres_filter(signal, kind, downsamp_t, downsamp_xz):
     """The reference's pre-filter of the high-res crop (dataloader_spacetime.py:96-116) on a [..., T, Z, X] tensor:
     scipy.ndimage gaussian (sigma = int(downsamp/2) per axis, truncate 4), uniform / median / maximum over a
@@ -59,22 +82,11 @@ def lres_filter(signal, kind, downsamp_t, downsamp_xz):
     if kind == 'none' or not kind:
         return signal
     sizes = (downsamp_t * 2 - 1, downsamp_xz * 2 - 1, downsamp_xz * 2 - 1)
-    if kind == 'gaussian':
+    if kind in ('gaussian', 'uniform'):
         out = signal
-        for dim, sigma in zip((-3, -2, -1), (int(downsamp_t / 2), int(downsamp_xz / 2), int(downsamp_xz / 2))):
-            if sigma <= 0:
-                continue
-            r = int(4.0 * sigma + 0.5)
-            k = torch.arange(-r, r + 1, device=signal.device, dtype=torch.float64)
-            w = torch.exp(-0.5 * k * k / (sigma * sigma))
-            out = _correlate_axis(out, (w / w.sum()).to(signal.dtype), signal.dim() + dim)
-        return out
-    if kind == 'uniform':
-        out = signal
-        for dim, sz in zip((-3, -2, -1), sizes):
-            if sz > 1:
-                out = _correlate_axis(out, torch.full((sz,), 1.0 / sz, device=signal.device, dtype=signal.dtype),
-                                      signal.dim() + dim)
+        for dim, w in zip((-3, -2, -1), filter_axis_weights(kind, downsamp_t, downsamp_xz, signal.device, signal.dtype)):
+            if w is not None:
+                out = _correlate_axis(out, w, signal.dim() + dim)
         return out
     if kind == 'maximum':
         return _window_view(signal, sizes).amax(dim=-1)
@@ -273,12 +285,25 @@ class DeviceBatchSampler:
         ids, pts = sampler.expected(k)                           # host model: what draw number k produced / will produce
 
     Every buffer a draw touches is allocated here, once: a captured graph replays addresses.  ``GraphedStep(sampler=...)`` puts
-    the draw at the head of every replay.  Loaders with an ``lres_filter`` are refused (``RB2DeviceLoader.get()`` filters)."""
+    the draw at the head of every replay.
 
-    def __init__(self, loader, batch_size, seed=0):
-        if loader.lres_filter and loader.lres_filter != 'none':
+    Loaders with an ``lres_filter`` are refused by default (``RB2DeviceLoader.get()`` filters).  ``filter_on_device=True``
+    accepts ``gaussian`` / ``uniform`` / ``maximum``: every batch is then draw -> up to three 1-D filter passes over two
+    scratch crops [B, nt, nz, nx, 4] allocated here (``stpde_sampler_filter``) -> the gather from the filtered crops
+    (``stpde_sampler_produce_filtered``), still bit-identical to ``loader.get()``.  ``median`` stays refused (not separable: a
+    selection kernel of its own).  The filter kind and its weight tables are fixed HERE: changing ``loader.lres_filter``
+    (or the down-sampling factors) afterwards has no effect on the sampler."""
+
+    def __init__(self, loader, batch_size, seed=0, filter_on_device=False):
+        kind = loader.lres_filter if loader.lres_filter and loader.lres_filter != 'none' else None
+        if kind and not filter_on_device:
             raise NotImplementedError("DeviceBatchSampler does not filter (lres_filter=%r): RB2DeviceLoader.get() is the path "
-                                      "that applies the low-res filters" % (loader.lres_filter,))
+                                      "that applies the low-res filters (filter_on_device=True filters gaussian / uniform / "
+                                      "maximum in the sampler)" % (kind,))
+        if kind and kind not in ('gaussian', 'uniform', 'maximum'):
+            raise NotImplementedError("DeviceBatchSampler(filter_on_device=True) has no kernel for lres_filter=%r (gaussian / "
+                                      "uniform / maximum are built): RB2DeviceLoader.get() is the path that applies it"
+                                      % (kind,))
         if int(batch_size) <= 0:
             raise ValueError("batch_size must be positive")
         if not loader.data_cl.is_cuda:
@@ -323,6 +348,26 @@ class DeviceBatchSampler:
         self.point_value = torch.zeros(B, N, 4, device=dev)
         self.crop_idx = torch.zeros(B, dtype=torch.int32, device=dev)
         self._state = torch.zeros(4, dtype=torch.int64, device=dev)     # stpde_sampler_state: seed, offset, oob | pad, pad
+        self.filter = kind
+        if kind:
+            f = _lib.SamplerFilterDesc()
+            f.T, f.Z, f.X = d.T, d.Z, d.X
+            f.nt, f.nz, f.nx = n
+            f.rt, f.rz, f.rx = loader._ranges
+            f.B, f.kind = B, _lib.FILTER_KINDS[kind]
+            if kind == 'maximum':
+                self._weights = [None, None, None]
+                radii = (loader.downsamp_t - 1, loader.downsamp_xz - 1, loader.downsamp_xz - 1)      # window 2 ds - 1
+            else:
+                # built on the loader's device with lres_filter's own expressions: the very tables get() multiplies by
+                self._weights = [None if w is None else w.contiguous()
+                                 for w in filter_axis_weights(kind, loader.downsamp_t, loader.downsamp_xz, dev)]
+                radii = [0 if w is None else (w.numel() - 1) // 2 for w in self._weights]
+            for k in range(3):
+                f.r[k] = radii[k]
+                f.nw[k] = 0 if self._weights[k] is None else self._weights[k].numel()
+            self._fdesc = f
+            self._scratch = (torch.zeros(B, *n, 4, device=dev), torch.zeros(B, *n, 4, device=dev))     # ping-pong crops
         self.seed(seed)
 
     def __len__(self):
@@ -367,13 +412,23 @@ class DeviceBatchSampler:
     def _produce(self, crop_idx, point_coord):
         import ctypes as C
         from . import _lib
+        if self.filter:
+            w, (sa, sb) = self._weights, self._scratch
+            _lib.check(_lib.lib().stpde_sampler_filter(
+                C.byref(self._fdesc), _lib.ptr(self._state), _lib.ptr(self.loader.data_cl), _lib.ptr(crop_idx), _lib.ptr(w[0]),
+                _lib.ptr(w[1]), _lib.ptr(w[2]), _lib.ptr(sa), _lib.ptr(sb), _lib.stream_ptr()))
+            _lib.check(_lib.lib().stpde_sampler_produce_filtered(
+                C.byref(self._desc), _lib.ptr(sa), _lib.ptr(self._taps[0]), _lib.ptr(self._taps[1]), _lib.ptr(self._taps[2]),
+                _lib.ptr(point_coord), _lib.ptr(self.lres), _lib.ptr(self.point_value), _lib.stream_ptr()))
+            return
         _lib.check(_lib.lib().stpde_sampler_produce(
             C.byref(self._desc), _lib.ptr(self._state), _lib.ptr(self.loader.data_cl), _lib.ptr(self._taps[0]),
             _lib.ptr(self._taps[1]), _lib.ptr(self._taps[2]), _lib.ptr(crop_idx), _lib.ptr(point_coord), _lib.ptr(self.lres),
             _lib.ptr(self.point_value), _lib.stream_ptr()))
 
     def draw(self):
-        """Next batch: two library calls on the current stream (capturable), no allocation, no synchronisation.  Returns the
+        """Next batch: two library calls on the current stream (three with a filter: draw, filter passes, produce from the
+        filtered crops), capturable, no allocation, no synchronisation.  Returns the
         static (lres [B,4,nt_l,nz_l,nx_l], point_coord [B,N,3], point_value [B,N,4]); ``crop_idx`` holds the ids."""
         import ctypes as C
         from . import _lib

@@ -12,6 +12,10 @@ query points per crop; synthetic RB2 run [4, 200, 512, 128], normalised outputs)
     (a) ``loader.get()`` in Python, then ``GraphedStep(optimizer=...)`` replayed on the copied-in batch;
     (b) ``GraphedStep(optimizer=..., sampler=...)``: the draw is the head of the graph, one replay is the whole iteration.
 
+``--lres-filter gaussian | uniform | maximum`` turns the reference's low-res pre-filter on in both loaders: ``get()`` then filters
+with composed torch ops per batch (``dataloader_spacetime.lres_filter``), ``draw()`` with the filter passes of csrc/sampler.hip
+(``DeviceBatchSampler(filter_on_device=True)``); results of such a run belong in ``profiles/sampler_filter.json``.
+
 Both members of a pair are timed alternately, so that drift of the box hits both alike.  Every sample and the medians go to
 ``--out`` (JSON); the last line printed is that JSON.  No target is attached to these numbers.
 
@@ -46,6 +50,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--samples", type=int, default=3)
     ap.add_argument("--skip-iteration", action="store_true", help="only the per-batch pair")
+    ap.add_argument("--lres-filter", default="none", choices=["none", "gaussian", "uniform", "maximum"],
+                    help="low-res pre-filter of both loaders (draw() then filters on the device)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -81,13 +87,15 @@ def main():
         return sa, sb
 
     out = {"device": torch.cuda.get_device_name(0), "samples": args.samples, "warmup": args.warmup,
-           "dataset": "synthetic RB2 run [4, 200, 512, 128] fp32, normalize_output=True, lres_filter none, linear",
+           "dataset": "synthetic RB2 run [4, 200, 512, 128] fp32, normalize_output=True, lres_filter %s, linear" % args.lres_filter,
+           "lres_filter": args.lres_filter,
            "per_batch": {}}
     data = torch.randn(4, 200, 512, 128, generator=torch.Generator().manual_seed(0))
     ld = RB2DeviceLoader(data, nx=128, nz=128, nt=16, n_samp_pts_per_crop=1024, downsamp_xz=4, downsamp_t=4,
-                         normalize_output=True, device=dev)
+                         normalize_output=True, device=dev, lres_filter=args.lres_filter)
+    on_device = args.lres_filter != "none"
     for nb in (10, 64):
-        s = DeviceBatchSampler(ld, nb, seed=0)
+        s = DeviceBatchSampler(ld, nb, seed=0, filter_on_device=on_device)
         gen = torch.Generator().manual_seed(nb)
 
         def get():
@@ -107,7 +115,7 @@ def main():
         unet = unet3d.UNet3d(in_features=4, out_features=32, igres=IGRES, nf=16, mf=256).to(dev).train()
         data = torch.randn(4, 64, 128, 128, generator=torch.Generator().manual_seed(2))
         ld = RB2DeviceLoader(data, nx=32, nz=32, nt=8, n_samp_pts_per_crop=N, downsamp_xz=2, downsamp_t=2,
-                             normalize_output=True, device=dev)
+                             normalize_output=True, device=dev, lres_filter=args.lres_filter)
         n0 = lig.stats["hip_jet_calls"]
         gen = torch.Generator().manual_seed(3)
 
@@ -126,7 +134,7 @@ def main():
         unet_b, net_b = copy.deepcopy(unet), copy.deepcopy(net)
         opt_b = optim.FusedClipAdam(list(unet_b.parameters()) + list(net_b.parameters()), lr=1e-2, clip_grad=1.0, flat=False,
                                     capturable=True)
-        s = DeviceBatchSampler(ld, B, seed=0)
+        s = DeviceBatchSampler(ld, B, seed=0, filter_on_device=on_device)
         gstep_b = GraphedStep(unet_b, net_b, physics.get_rb2_pde_layer(**RB2), None, None, None, N, ALPHA_REG, ALPHA_PDE, "l1",
                               optimizer=opt_b, sampler=s)
         assert lig.stats["hip_jet_calls"] > n0, "HIP jet path was not taken"

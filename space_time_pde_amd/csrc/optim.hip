@@ -4,6 +4,57 @@
 // written (p, m, v) per element, float4 accesses, grid-stride.
 #include "common.h"
 
+// ---- the two traversals every update kernel is made of -------------------------------------------------------------
+// quad(e) updates the four elements from e on with float4 accesses (e a multiple of 4, the pointers 16-byte aligned),
+// one(e) a single element.
+
+// Flat pass over n elements: grid-stride over the quads, the n % 4 tail by block 0.
+template <class Quad, class One>
+__device__ __forceinline__ void flat_pass(long n, Quad quad, One one) {
+  const long n4 = n / 4;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) quad(4 * i);
+  if (blockIdx.x == 0) {  // tail (n not a multiple of 4)
+    const long i = n4 * 4 + threadIdx.x;
+    if (i < n) one(i);
+  }
+}
+
+// Multi-tensor pass: ONE launch updates every parameter tensor of the model.  Block b works on chunk b of the chunk
+// table (tensor index, element offset): elements [c.offset, min(c.offset + chunk_elems, n)) of an n-element tensor.
+template <class Quad, class One>
+__device__ __forceinline__ void chunk_pass(const stpde_adam_chunk& c, long n, int chunk_elems, Quad quad, One one) {
+  const long lo = c.offset;
+  const long hi = lo + chunk_elems < n ? lo + chunk_elems : n;
+  const long n4 = (hi - lo) / 4;           // offsets are multiples of 4 and the pointers 16-byte aligned
+  for (long i = threadIdx.x; i < n4; i += 256) quad(lo + 4 * i);
+  const long e = lo + 4 * n4 + threadIdx.x;
+  if (e < hi) one(e);
+}
+
+// grid of a flat pass: one quad per thread, at most 2048 blocks
+static dim3 flat_grid(long n) {
+  long blocks = (n / 4 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  return dim3((unsigned)blocks);
+}
+
+// argument check of the four table entry points.  desc_ok: the caller's own check of its descriptor; aligned: state block and
+// tables must be 16-byte aligned (every entry point but the oldest, stpde_clip_adam_multi, whose contract never said so)
+static int check_tables(const char* who, bool desc_ok, bool aligned, const void* state_dev, const void* tensors_dev,
+                        const void* chunks_dev, int nchunks, int chunk_elems) {
+  if (!desc_ok || !tensors_dev || !chunks_dev || nchunks <= 0 || chunk_elems <= 0 || (chunk_elems & 3)) {
+    stpde_set_error("%s: bad argument (chunk_elems must be a positive multiple of 4)", who);
+    return STPDE_E_BADARG;
+  }
+  if (aligned && (((size_t)state_dev | (size_t)tensors_dev | (size_t)chunks_dev) & 15)) {
+    stpde_set_error("%s: state block and tables must be 16-byte aligned", who);
+    return STPDE_E_BADARG;
+  }
+  return STPDE_OK;
+}
+
+// ---- Adam ----------------------------------------------------------------------------------------------------------
 struct AdamArgs {
   stpde_adam_desc d;
   float* p;
@@ -21,77 +72,57 @@ __device__ __forceinline__ void adam_elem(const stpde_adam_desc& d, float& p, fl
   p = p - d.step_size * (m / denom);                             // addcdiv_(exp_avg, denom, value=-lr/bias1)
 }
 
-__global__ __launch_bounds__(256) void k_clip_adam(AdamArgs a) {
-  const long n4 = a.d.n / 4;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-    f32x4 p = ld4(a.p + 4 * i), g = ld4(a.g + 4 * i), m = ld4(a.m + 4 * i), v = ld4(a.v + 4 * i);
+__device__ __forceinline__ void adam_quad(const stpde_adam_desc& d, float* P, const float* G, float* M, float* V, long e) {
+  f32x4 p = ld4(P + e), g = ld4(G + e), m = ld4(M + e), v = ld4(V + e);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float pp = p[r], mm = m[r], vv = v[r];
-      adam_elem(a.d, pp, g[r], mm, vv);
-      p[r] = pp;
-      m[r] = mm;
-      v[r] = vv;
-    }
-    st4(a.p + 4 * i, p);
-    st4(a.m + 4 * i, m);
-    st4(a.v + 4 * i, v);
+  for (int r = 0; r < 4; ++r) {
+    float pp = p[r], mm = m[r], vv = v[r];
+    adam_elem(d, pp, g[r], mm, vv);
+    p[r] = pp;
+    m[r] = mm;
+    v[r] = vv;
   }
-  if (blockIdx.x == 0) {  // tail (n not a multiple of 4)
-    const long i = n4 * 4 + threadIdx.x;
-    if (i < a.d.n) {
-      float pp = a.p[i], mm = a.m[i], vv = a.v[i];
-      adam_elem(a.d, pp, a.g[i], mm, vv);
-      a.p[i] = pp;
-      a.m[i] = mm;
-      a.v[i] = vv;
-    }
-  }
+  st4(P + e, p);
+  st4(M + e, m);
+  st4(V + e, v);
 }
 
-// Multi-tensor variant: ONE launch updates every parameter tensor of the model.  Block b works on chunk b of the
-// chunk table (tensor index, element offset); the tensor table holds the four pointers, the length and the
-// bias-correction factors (tensors may have different step counts).
+__device__ __forceinline__ void adam_one(const stpde_adam_desc& d, float* P, const float* G, float* M, float* V, long e) {
+  float pp = P[e], mm = M[e], vv = V[e];
+  adam_elem(d, pp, G[e], mm, vv);
+  P[e] = pp;
+  M[e] = mm;
+  V[e] = vv;
+}
+
+// d carries step_size / bias2_sqrt: the caller's host scalars, or the state block's (the _dev kernels)
+__device__ __forceinline__ void adam_flat(const stpde_adam_desc& d, const AdamArgs& a) {
+  flat_pass(d.n, [&](long e) { adam_quad(d, a.p, a.g, a.m, a.v, e); }, [&](long e) { adam_one(d, a.p, a.g, a.m, a.v, e); });
+}
+
+__device__ __forceinline__ void adam_chunk(const stpde_adam_desc& d, const stpde_adam_tensor& t, const stpde_adam_chunk& c,
+                                           int chunk_elems) {
+  chunk_pass(c, t.n, chunk_elems, [&](long e) { adam_quad(d, t.p, t.g, t.m, t.v, e); },
+             [&](long e) { adam_one(d, t.p, t.g, t.m, t.v, e); });
+}
+
+__global__ __launch_bounds__(256) void k_clip_adam(AdamArgs a) { adam_flat(a.d, a); }
+
+// The tensor table holds the four pointers, the length and the bias-correction factors (tensors may have different
+// step counts).
 __global__ __launch_bounds__(256) void k_clip_adam_multi(stpde_adam_desc d, const stpde_adam_tensor* tensors,
                                                          const stpde_adam_chunk* chunks, int chunk_elems) {
   const stpde_adam_chunk c = chunks[blockIdx.x];
   const stpde_adam_tensor t = tensors[c.tensor];
   d.step_size = t.step_size;
   d.bias2_sqrt = t.bias2_sqrt;
-  const long lo = c.offset;
-  const long hi = lo + chunk_elems < t.n ? lo + chunk_elems : t.n;
-  const long n4 = (hi - lo) / 4;           // offsets are multiples of 4 and the pointers 16-byte aligned
-  for (long i = threadIdx.x; i < n4; i += 256) {
-    const long e = lo + 4 * i;
-    f32x4 p = ld4(t.p + e), g = ld4(t.g + e), m = ld4(t.m + e), v = ld4(t.v + e);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float pp = p[r], mm = m[r], vv = v[r];
-      adam_elem(d, pp, g[r], mm, vv);
-      p[r] = pp;
-      m[r] = mm;
-      v[r] = vv;
-    }
-    st4(t.p + e, p);
-    st4(t.m + e, m);
-    st4(t.v + e, v);
-  }
-  const long e = lo + 4 * n4 + threadIdx.x;
-  if (e < hi) {
-    float pp = t.p[e], mm = t.m[e], vv = t.v[e];
-    adam_elem(d, pp, t.g[e], mm, vv);
-    t.p[e] = pp;
-    t.m[e] = mm;
-    t.v[e] = vv;
-  }
+  adam_chunk(d, t, c, chunk_elems);
 }
 
 extern "C" int stpde_clip_adam_multi(const stpde_adam_desc* d, const stpde_adam_tensor* tensors_dev,
                                      const stpde_adam_chunk* chunks_dev, int nchunks, int chunk_elems, void* stream) {
-  if (!d || !tensors_dev || !chunks_dev || nchunks <= 0 || chunk_elems <= 0 || (chunk_elems & 3)) {
-    stpde_set_error("clip_adam_multi: bad argument (chunk_elems must be a positive multiple of 4)");
-    return STPDE_E_BADARG;
-  }
+  if (int rc = check_tables("clip_adam_multi", d != nullptr, false, nullptr, tensors_dev, chunks_dev, nchunks, chunk_elems))
+    return rc;
   STPDE_LAUNCH(k_clip_adam_multi, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, *d, tensors_dev,
                chunks_dev, chunk_elems);
   return stpde_check_launch("k_clip_adam_multi");
@@ -108,10 +139,7 @@ extern "C" int stpde_clip_adam(const stpde_adam_desc* d, float* param, const flo
     return STPDE_E_BADARG;
   }
   AdamArgs a{*d, param, grad, exp_avg, exp_avg_sq};
-  long blocks = (d->n / 4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  STPDE_LAUNCH(k_clip_adam, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  STPDE_LAUNCH(k_clip_adam, flat_grid(d->n), dim3(256), 0, (hipStream_t)stream, a);
   return stpde_check_launch("k_clip_adam");
 }
 
@@ -139,40 +167,11 @@ extern "C" int stpde_opt_advance(const stpde_opt_desc* d, stpde_opt_state* state
   return stpde_check_launch("k_opt_advance");
 }
 
-__device__ __forceinline__ void adam_quad(const stpde_adam_desc& d, float* P, const float* G, float* M, float* V, long e) {
-  f32x4 p = ld4(P + e), g = ld4(G + e), m = ld4(M + e), v = ld4(V + e);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float pp = p[r], mm = m[r], vv = v[r];
-    adam_elem(d, pp, g[r], mm, vv);
-    p[r] = pp;
-    m[r] = mm;
-    v[r] = vv;
-  }
-  st4(P + e, p);
-  st4(M + e, m);
-  st4(V + e, v);
-}
-
-__device__ __forceinline__ void adam_one(const stpde_adam_desc& d, float* P, const float* G, float* M, float* V, long e) {
-  float pp = P[e], mm = M[e], vv = V[e];
-  adam_elem(d, pp, G[e], mm, vv);
-  P[e] = pp;
-  M[e] = mm;
-  V[e] = vv;
-}
-
 // k_clip_adam with step_size / bias2_sqrt read from the state block (written by the k_opt_advance in front of it)
 __global__ __launch_bounds__(256) void k_clip_adam_dev(AdamArgs a, const stpde_opt_state* s) {
   a.d.step_size = s->step_size;
   a.d.bias2_sqrt = s->bias2_sqrt;
-  const long n4 = a.d.n / 4;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256)
-    adam_quad(a.d, a.p, a.g, a.m, a.v, 4 * i);
-  if (blockIdx.x == 0) {  // tail (n not a multiple of 4)
-    const long i = n4 * 4 + threadIdx.x;
-    if (i < a.d.n) adam_one(a.d, a.p, a.g, a.m, a.v, i);
-  }
+  adam_flat(a.d, a);
 }
 
 // k_clip_adam_multi with ONE step count for all tensors: the tables hold pointers and lengths only, so the caller builds
@@ -184,12 +183,7 @@ __global__ __launch_bounds__(256) void k_clip_adam_multi_dev(stpde_adam_desc d, 
   const stpde_adam_tensor t = tensors[c.tensor];
   d.step_size = s->step_size;
   d.bias2_sqrt = s->bias2_sqrt;
-  const long lo = c.offset;
-  const long hi = lo + chunk_elems < t.n ? lo + chunk_elems : t.n;
-  const long n4 = (hi - lo) / 4;           // offsets are multiples of 4 and the pointers 16-byte aligned
-  for (long i = threadIdx.x; i < n4; i += 256) adam_quad(d, t.p, t.g, t.m, t.v, lo + 4 * i);
-  const long e = lo + 4 * n4 + threadIdx.x;
-  if (e < hi) adam_one(d, t.p, t.g, t.m, t.v, e);
+  adam_chunk(d, t, c, chunk_elems);
 }
 
 static bool adam_desc_ok(const stpde_adam_desc* d) {
@@ -207,25 +201,16 @@ extern "C" int stpde_clip_adam_dev(const stpde_adam_desc* d, const stpde_opt_sta
     return STPDE_E_BADARG;
   }
   AdamArgs a{*d, param, grad, exp_avg, exp_avg_sq};
-  long blocks = (d->n / 4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  STPDE_LAUNCH(k_clip_adam_dev, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, state_dev);
+  STPDE_LAUNCH(k_clip_adam_dev, flat_grid(d->n), dim3(256), 0, (hipStream_t)stream, a, state_dev);
   return stpde_check_launch("k_clip_adam_dev");
 }
 
 extern "C" int stpde_clip_adam_multi_dev(const stpde_adam_desc* d, const stpde_opt_state* state_dev,
                                          const stpde_adam_tensor* tensors_dev, const stpde_adam_chunk* chunks_dev,
                                          int nchunks, int chunk_elems, void* stream) {
-  if (!adam_desc_ok(d) || !state_dev || !tensors_dev || !chunks_dev || nchunks <= 0 || chunk_elems <= 0 ||
-      (chunk_elems & 3)) {
-    stpde_set_error("clip_adam_multi_dev: bad argument (chunk_elems must be a positive multiple of 4)");
-    return STPDE_E_BADARG;
-  }
-  if (((size_t)state_dev | (size_t)tensors_dev | (size_t)chunks_dev) & 15) {
-    stpde_set_error("clip_adam_multi_dev: state block and tables must be 16-byte aligned");
-    return STPDE_E_BADARG;
-  }
+  if (int rc = check_tables("clip_adam_multi_dev", adam_desc_ok(d) && state_dev, true, state_dev, tensors_dev, chunks_dev, nchunks,
+                            chunk_elems))
+    return rc;
   STPDE_LAUNCH(k_clip_adam_multi_dev, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, *d, state_dev,
                tensors_dev, chunks_dev, chunk_elems);
   return stpde_check_launch("k_clip_adam_multi_dev");
@@ -291,12 +276,7 @@ struct SgdArgs {
 
 __global__ __launch_bounds__(256) void k_clip_sgd(SgdArgs a) {
   const SgdRule r = sgd_rule(a.d, a.s, a.d.first_step);
-  const long n4 = a.d.n / 4;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) sgd_quad(r, a.p, a.g, a.b, 4 * i);
-  if (blockIdx.x == 0) {  // tail (n not a multiple of 4)
-    const long i = n4 * 4 + threadIdx.x;
-    if (i < a.d.n) sgd_one(r, a.p, a.g, a.b, i);
-  }
+  flat_pass(a.d.n, [&](long e) { sgd_quad(r, a.p, a.g, a.b, e); }, [&](long e) { sgd_one(r, a.p, a.g, a.b, e); });
 }
 
 __global__ __launch_bounds__(256) void k_clip_sgd_multi(stpde_sgd_desc d, const stpde_opt_state* s,
@@ -305,12 +285,8 @@ __global__ __launch_bounds__(256) void k_clip_sgd_multi(stpde_sgd_desc d, const 
   const stpde_adam_chunk c = chunks[blockIdx.x];
   const stpde_sgd_tensor t = tensors[c.tensor];
   const SgdRule r = sgd_rule(d, s, t.first_step);
-  const long lo = c.offset;
-  const long hi = lo + chunk_elems < t.n ? lo + chunk_elems : t.n;
-  const long n4 = (hi - lo) / 4;           // offsets are multiples of 4 and the pointers 16-byte aligned
-  for (long i = threadIdx.x; i < n4; i += 256) sgd_quad(r, t.p, t.g, t.buf, lo + 4 * i);
-  const long e = lo + 4 * n4 + threadIdx.x;
-  if (e < hi) sgd_one(r, t.p, t.g, t.buf, e);
+  chunk_pass(c, t.n, chunk_elems, [&](long e) { sgd_quad(r, t.p, t.g, t.buf, e); },
+             [&](long e) { sgd_one(r, t.p, t.g, t.buf, e); });
 }
 
 static bool sgd_desc_ok(const stpde_sgd_desc* d) {
@@ -328,24 +304,15 @@ extern "C" int stpde_clip_sgd(const stpde_sgd_desc* d, const stpde_opt_state* st
     return STPDE_E_BADARG;
   }
   SgdArgs a{*d, state_dev, param, grad, momentum_buf};
-  long blocks = (d->n / 4 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  STPDE_LAUNCH(k_clip_sgd, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  STPDE_LAUNCH(k_clip_sgd, flat_grid(d->n), dim3(256), 0, (hipStream_t)stream, a);
   return stpde_check_launch("k_clip_sgd");
 }
 
 extern "C" int stpde_clip_sgd_multi(const stpde_sgd_desc* d, const stpde_opt_state* state_dev,
                                     const stpde_sgd_tensor* tensors_dev, const stpde_adam_chunk* chunks_dev, int nchunks,
                                     int chunk_elems, void* stream) {
-  if (!sgd_desc_ok(d) || !tensors_dev || !chunks_dev || nchunks <= 0 || chunk_elems <= 0 || (chunk_elems & 3)) {
-    stpde_set_error("clip_sgd_multi: bad argument (chunk_elems must be a positive multiple of 4)");
-    return STPDE_E_BADARG;
-  }
-  if (((size_t)state_dev | (size_t)tensors_dev | (size_t)chunks_dev) & 15) {
-    stpde_set_error("clip_sgd_multi: state block and tables must be 16-byte aligned");
-    return STPDE_E_BADARG;
-  }
+  if (int rc = check_tables("clip_sgd_multi", sgd_desc_ok(d), true, state_dev, tensors_dev, chunks_dev, nchunks, chunk_elems))
+    return rc;
   STPDE_LAUNCH(k_clip_sgd_multi, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, *d, state_dev, tensors_dev,
                chunks_dev, chunk_elems);
   return stpde_check_launch("k_clip_sgd_multi");

@@ -167,6 +167,56 @@ def test_capturable_adam_tracks_the_host_scalar_path_over_50_steps(hiplib, flat)
     assert worst < TOL
 
 
+HOST_KINDS = {
+    "adam": dict(),
+    "sgd_momentum": dict(momentum=0.9, dampening=0.1),
+    "sgd_plain": dict(),
+}
+# FusedClipSGD(flat=True): the steps that leave the flat kernel for the pointer table -- a missing gradient (steps 0 and 3)
+# and, with momentum, step 1, where parameter 2 takes its first momentum step and the others their second
+SGD_TABLE_STEPS = {"sgd_momentum": (0, 1, 3), "sgd_plain": (0, 3)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flat", [True, False])
+@pytest.mark.parametrize("kind", sorted(HOST_KINDS))
+def test_host_scalar_fallbacks_match_torch_across_a_chunk_boundary(hiplib, kind, flat):
+    """capturable=False over six steps with a missing gradient at step 0 (parameter 2) and at step 3 (parameter 4), on SHAPES
+    plus a tensor of 65543 elements: one past the 65536-element chunk of the table kernels, i.e. a second chunk of one float4
+    and a 3-element tail.  Against clip_grad_value_ (on the parameters that have a gradient) + torch.optim.Adam / SGD, which
+    skip a parameter without a gradient; and the kernel each step takes: the pointer table for every ``flat=False`` step, for
+    every Adam step (the step counts differ from step 0 on and never re-equalise) and for SGD's SGD_TABLE_STEPS, else the
+    flat kernel."""
+    from space_time_pde_amd import _lib
+    from space_time_pde_amd.optim import _CHUNK, FusedClipAdam, FusedClipSGD
+    assert _CHUNK == 65536
+    shapes = SHAPES + [(_CHUNK + 7,)]
+    missing = {0: 2, 3: 4}
+    g = torch.Generator().manual_seed(3)
+    pa = [torch.randn(s, generator=g).to(DEV).requires_grad_(True) for s in shapes]
+    pb = [p.detach().clone().requires_grad_(True) for p in pa]
+    kw = HOST_KINDS[kind]
+    if kind == "adam":
+        oa, ob, name = FusedClipAdam(pa, lr=LR, clip_grad=CLIP, flat=flat), torch.optim.Adam(pb, lr=LR), "k_clip_adam"
+    else:
+        oa, ob, name = FusedClipSGD(pa, lr=LR, clip_grad=CLIP, flat=flat, **kw), torch.optim.SGD(pb, lr=LR, **kw), "k_clip_sgd"
+    for it in range(6):
+        grads = [torch.randn(s, generator=g).to(DEV) * 2.0 for s in shapes]
+        for k, (p, q, gr) in enumerate(zip(pa, pb, grads)):
+            p.grad, q.grad = (None, None) if missing.get(it) == k else (gr.clone(), gr.clone())
+        torch.nn.utils.clip_grad_value_([q for q in pb if q.grad is not None], CLIP)
+        with _lib.dispatch_trace() as tr:
+            oa.step()
+        table = (not flat) or kind == "adam" or it in SGD_TABLE_STEPS[kind]
+        print("%s flat=%s step %d: %s" % (kind, flat, it, tr.kernels))
+        assert tr.has(name + "_multi @") == table and tr.has(name + " @") == (not table), (it, tr.kernels)
+        assert len(tr.kernels) == 1, tr.kernels
+        ob.step()
+        err = _maxdiff(pa, pb)
+        print("%s flat=%s step %d: max |p - torch| = %.3e" % (kind, flat, it, err))
+        assert err < TOL
+
+
 class _Ops(TorchDispatchMode):
     """Every torch operator dispatched inside the block (copies, fills, uploads included), but for the record_function
     markers torch.optim.Optimizer wraps around every ``step()`` (``profiler.*``: no tensor work)."""

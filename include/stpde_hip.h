@@ -767,7 +767,7 @@ int stpde_sampler_produce(const stpde_sampler_desc* d, stpde_sampler_state* stat
  * What RB2DeviceLoader.get() does with dataloader_spacetime.lres_filter before it interpolates (reference
  * experiments/rb2d/dataloader_spacetime.py:96-116, :136-155), bit for bit, in capturable launches: the high-res crops of the
  * batch are filtered into a scratch crop, and BOTH outputs are then interpolated from it by the produce entry below.
- * `median` has no kernel (not separable; a selection over 7 * 15 * 15 values at the reference's sizes).
+ * `median` is not separable and has an entry of its own, stpde_sampler_median below.
  *
  * The filter acts on the crop [nt][nz][nx] per channel with scipy's 'reflect' boundary at the CROP faces (the edge sample is
  * repeated, period 2n, any radius); dataset values outside the crop are never read.  Up to three 1-D passes run in the order
@@ -800,6 +800,29 @@ int stpde_sampler_filter(const stpde_sampler_filter_desc* d, stpde_sampler_state
 int stpde_sampler_produce_filtered(const stpde_sampler_desc* d, const float* crops, const stpde_sampler_tap* taps_t,
                                    const stpde_sampler_tap* taps_z, const stpde_sampler_tap* taps_x, const float* point_coord,
                                    float* lres_out, float* point_value_out, void* stream);
+
+/* ---- N3 on the device, the median pre-filter (lres_filter = median) --------------------------------------------
+ * The fourth filter of the reference loader: per voxel and channel the element of rank (W - 1) / 2 (ascending, 0-based) of the
+ * W = (2 r_t + 1)(2 r_z + 1)(2 r_x + 1) values of its window -- W is odd, so this is the exact median, what
+ * RB2DeviceLoader.get() computes by unfolding every window and torch.median.  Not separable: ONE selection kernel (csrc/
+ * sampler_median.hip: a tile and its halo staged into LDS as order-preserving keys, MSB-first radix selection per voxel).
+ *   d          the filter descriptor above with kind = STPDE_FILTER_MEDIAN, nw[k] = 0 and r[k] in [0, 7] (downsamp - 1; a larger
+ *              halo does not fit the LDS of one workgroup and is refused).  r[k] = 0 is a window of 1 along that axis, not a
+ *              skipped pass; all radii 0 is a plain copy of the crops.
+ *   window     scipy's 'reflect' rule at the CROP faces (period 2n, valid for r >= n), the index formula of the 1-D passes;
+ *              dataset values outside the crop are never read.
+ *   NaN        a window that holds a NaN gives a (quiet) NaN, as torch.median.  Of zeros of both signs either may be returned.
+ *   crops_out  [B][nt][nz][nx][4] fp32, 16-byte aligned: the layout of scratch_a, consumed as it is by
+ *              stpde_sampler_produce_filtered.
+ * crop_idx is clamped into [0, len) before any address is formed and a clamped id is counted once in state->oob, as above.
+ * Nothing allocates or synchronises; apart from that count there are no atomics, so the result is the same every run.
+ * stpde_sampler_filter keeps refusing kind 4.
+ * Cost (an ESTIMATE, not a measurement): at the reference's training shape (B = 10, crop 16 x 128 x 128, r = 3: W = 343)
+ * 2.6 M voxels x 343 taps x up to 32 walks x 16 B are about 4.6e11 B of LDS reads, a few ms at the LDS rate of the part.  Follow-up,
+ * not built: select only at the nodes the two interpolations read (about 41 k of 262 k voxels per crop), roughly 6 x less. */
+#define STPDE_FILTER_MEDIAN 4     /* accepted by stpde_sampler_median only */
+int stpde_sampler_median(const stpde_sampler_filter_desc* d, stpde_sampler_state* state_dev, const float* data_cl,
+                         const int* crop_idx, float* crops_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 # STPDE_LIB: load another build of the library (A/B timing of kernel variants on one box; never set by tests or the driver)
 LIB_PATH = os.environ.get("STPDE_LIB") or os.path.join(_HERE, "libstpde_hip.so")
-_SOURCES = ["jet_layer.hip", "jet_layer_s00.hip", "jet_layer_s03.hip", "jet_layer_s30.hip", "jet_layer_s31.hip", "jet_layer_s32.hip", "jet_layer_s34.hip", "jet_layer_s36.hip", "jet_tail.hip", "jet_wgrad.hip", "jet_wgrad_s00.hip", "jet_wgrad_s30.hip", "jet_wgrad_s31.hip", "jet_wgrad_s32.hip", "jet_wgrad_s34.hip", "jet_wgrad_s36.hip", "jet_fc1_bwd.hip", "lig_gather_reduce.hip", "lig_pipeline.hip", "interp_nd.hip", "conv3d.hip", "conv3d_fused.hip", "optim.hip", "residual.hip", "bn.hip", "resample.hip", "sampler.hip", "api.cpp"]
+_SOURCES = ["jet_layer.hip", "jet_layer_s00.hip", "jet_layer_s03.hip", "jet_layer_s30.hip", "jet_layer_s31.hip", "jet_layer_s32.hip", "jet_layer_s34.hip", "jet_layer_s36.hip", "jet_tail.hip", "jet_wgrad.hip", "jet_wgrad_s00.hip", "jet_wgrad_s30.hip", "jet_wgrad_s31.hip", "jet_wgrad_s32.hip", "jet_wgrad_s34.hip", "jet_wgrad_s36.hip", "jet_fc1_bwd.hip", "lig_gather_reduce.hip", "lig_pipeline.hip", "interp_nd.hip", "conv3d.hip", "conv3d_fused.hip", "optim.hip", "residual.hip", "bn.hip", "resample.hip", "sampler.hip", "sampler_median.hip", "api.cpp"]
 # --offload-compress: the gfx950 code objects are stored zstd-compressed in the fat binary (the HIP runtime inflates them at
 # module load): libstpde_hip.so 68 MB -> ~1/4; the instruction bytes are the same (tools/check_dpp_hazard.py scans them)
 _HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics",
@@ -154,6 +154,8 @@ class SamplerFilterDesc(C.Structure):    # stpde_sampler_filter_desc
 
 
 FILTER_KINDS = {"gaussian": 1, "uniform": 2, "maximum": 3}     # STPDE_FILTER_*
+FILTER_MEDIAN = 4             # STPDE_FILTER_MEDIAN: stpde_sampler_median only (stpde_sampler_filter refuses it)
+FILTER_MEDIAN_MAX_RADIUS = 7  # tile + halo must fit the LDS of one workgroup (csrc/sampler_median.hip)
 
 
 def _sources():
@@ -302,6 +304,7 @@ _SIGNATURES = {
     "stpde_sampler_produce": ([C.POINTER(SamplerDesc)] + [_VP] * 10, C.c_int),
     "stpde_sampler_filter": ([C.POINTER(SamplerFilterDesc)] + [_VP] * 9, C.c_int),
     "stpde_sampler_produce_filtered": ([C.POINTER(SamplerDesc)] + [_VP] * 8, C.c_int),
+    "stpde_sampler_median": ([C.POINTER(SamplerFilterDesc)] + [_VP] * 5, C.c_int),
 }
 
 

@@ -10,6 +10,7 @@
 // With a low-res pre-filter (gaussian / uniform / maximum, stpde_sampler_filter) the crops ARE materialised: up to three 1-D
 // passes (t, then z, then x) over two caller-owned scratch crops [B][nt][nz][nx][4] that ping-pong, then the same gather with
 // crop-local addressing (k_sampler_produce_crop).  See "filter passes" below for the arithmetic and the address budget.
+// The median pre-filter is not separable: one selection kernel of its own in sampler_median.hip, feeding the same crop gather.
 #include "interp_geom.h"
 
 struct SamplerArgs {
@@ -411,7 +412,7 @@ extern "C" int stpde_sampler_filter(const stpde_sampler_filter_desc* d, stpde_sa
     return STPDE_E_BADARG;
   }
   if (d->kind != STPDE_FILTER_GAUSSIAN && d->kind != STPDE_FILTER_UNIFORM && d->kind != STPDE_FILTER_MAXIMUM) {
-    stpde_set_error("%s: kind must be 1 (gaussian), 2 (uniform) or 3 (maximum), got %d (median has no kernel)", who, d->kind);
+    stpde_set_error("%s: kind must be 1 (gaussian), 2 (uniform) or 3 (maximum), got %d (median, 4, is stpde_sampler_median's)", who, d->kind);
     return STPDE_E_BADARG;
   }
   const bool weighted = d->kind != STPDE_FILTER_MAXIMUM;

@@ -12,7 +12,9 @@ produced by the imported reference loader (tests/golden/n3_dataloader.npz).
 
 ``DeviceBatchSampler`` draws whole training batches of an ``RB2DeviceLoader`` on the device with capturable launches
 (csrc/sampler.hip), bit-identical to ``RB2DeviceLoader.get()`` on the same crop ids and points -- with
-``filter_on_device=True`` also for the gaussian / uniform / maximum pre-filters; ``sampler_expected`` is its host model.
+``filter_on_device=True`` also for the gaussian / uniform / maximum pre-filters and with ``median_on_device=True`` for the
+median one (csrc/sampler_median.hip; ``lres_median_device`` is that kernel on crops of the caller's own); ``sampler_expected``
+is its host model.
 """
 import os
 
@@ -78,7 +80,10 @@ def filter_axis_weights(kind, downsamp_t, downsamp_xz, device, dtype=torch.float
 def lres_filter(signal, kind, downsamp_t, downsamp_xz):
     """The reference's pre-filter of the high-res crop (dataloader_spacetime.py:96-116) on a [..., T, Z, X] tensor:
     scipy.ndimage gaussian (sigma = int(downsamp/2) per axis, truncate 4), uniform / median / maximum over a
-    (2 downsamp - 1) window, all with the 'reflect' boundary."""
+    (2 downsamp - 1) window, all with the 'reflect' boundary.
+
+    The median unfolds every voxel's whole window (prod(sizes) values per element) before ``torch.median``; it is NOT switched
+    over to the HIP selection kernel -- ``lres_median_device`` and ``DeviceBatchSampler(median_on_device=True)`` are."""
     if kind == 'none' or not kind:
         return signal
     sizes = (downsamp_t * 2 - 1, downsamp_xz * 2 - 1, downsamp_xz * 2 - 1)
@@ -93,6 +98,40 @@ def lres_filter(signal, kind, downsamp_t, downsamp_xz):
     if kind == 'median':
         return _window_view(signal, sizes).median(dim=-1).values     # window sizes are odd: the exact median
     raise NotImplementedError("lres_filter must be one of none/gaussian/uniform/median/maximum")
+
+
+def lres_median_device(crops_cl, radii):
+    """Median filter of channels-last crops [B, nt, nz, nx, 4] (fp32, contiguous, on a HIP device) over the window of
+    ``radii`` = (r_t, r_z, r_x), each in [0, 7], 'reflect' boundary at the crop faces: a new tensor of the same shape, equal to
+    ``lres_filter(crops.permute(0, 4, 1, 2, 3), 'median', r_t + 1, ...)`` but computed by the selection kernel of
+    csrc/sampler_median.hip (``stpde_sampler_median``) without unfolding the windows -- e.g. a whole evaluation crop.  A window
+    that holds a NaN gives NaN.  The batch is passed as a dataset [B * nt][nz][nx][4] with crop ids b * nt."""
+    import ctypes as C
+    from . import _lib
+    if not (torch.is_tensor(crops_cl) and crops_cl.is_cuda):
+        raise RuntimeError("lres_median_device needs a tensor on a HIP device")
+    if crops_cl.dim() != 5 or crops_cl.shape[-1] != 4 or crops_cl.dtype != torch.float32 or not crops_cl.is_contiguous():
+        raise ValueError("lres_median_device: crops must be [B, nt, nz, nx, 4] fp32 contiguous, got %s %s"
+                         % (tuple(crops_cl.shape), crops_cl.dtype))
+    radii = tuple(int(r) for r in radii)
+    if len(radii) != 3 or any(not 0 <= r <= _lib.FILTER_MEDIAN_MAX_RADIUS for r in radii):
+        raise NotImplementedError("lres_median_device: radii %r, each must be in [0, %d] (downsamp <= %d)"
+                                  % (radii, _lib.FILTER_MEDIAN_MAX_RADIUS, _lib.FILTER_MEDIAN_MAX_RADIUS + 1))
+    B, nt, nz, nx = crops_cl.shape[:4]
+    f = _lib.SamplerFilterDesc()
+    f.T, f.Z, f.X = B * nt, nz, nx
+    f.nt, f.nz, f.nx = nt, nz, nx
+    f.rt, f.rz, f.rx = B * nt - nt + 1, 1, 1
+    f.B, f.kind = B, _lib.FILTER_MEDIAN
+    for k in range(3):
+        f.r[k], f.nw[k] = radii[k], 0
+    with _lib.device_of(crops_cl):
+        out = torch.empty_like(crops_cl)
+        ids = torch.arange(0, B * nt, nt, dtype=torch.int32, device=crops_cl.device)
+        state = torch.zeros(4, dtype=torch.int64, device=crops_cl.device)
+        _lib.check(_lib.lib().stpde_sampler_median(C.byref(f), _lib.ptr(state), _lib.ptr(crops_cl), _lib.ptr(ids), _lib.ptr(out),
+                                                   _lib.stream_ptr()))
+    return out
 
 
 class RB2DeviceLoader:
@@ -290,20 +329,31 @@ class DeviceBatchSampler:
     Loaders with an ``lres_filter`` are refused by default (``RB2DeviceLoader.get()`` filters).  ``filter_on_device=True``
     accepts ``gaussian`` / ``uniform`` / ``maximum``: every batch is then draw -> up to three 1-D filter passes over two
     scratch crops [B, nt, nz, nx, 4] allocated here (``stpde_sampler_filter``) -> the gather from the filtered crops
-    (``stpde_sampler_produce_filtered``), still bit-identical to ``loader.get()``.  ``median`` stays refused (not separable: a
-    selection kernel of its own).  The filter kind and its weight tables are fixed HERE: changing ``loader.lres_filter``
+    (``stpde_sampler_produce_filtered``), still bit-identical to ``loader.get()``.  ``median`` is not separable and has a
+    switch of its own, ``median_on_device=True`` (together with ``filter_on_device=True``), because its cost class differs: the
+    other filters take microseconds, a selection over hundreds of window values per voxel takes milliseconds.  A batch is then
+    draw -> one selection kernel into ONE scratch crop (``stpde_sampler_median``, radii ``downsamp - 1`` <= 7) -> the same
+    gather, equal to ``loader.get()`` (NaN where it has NaN).  With any other loader ``median_on_device`` changes nothing.
+    The filter kind and its weight tables are fixed HERE: changing ``loader.lres_filter``
     (or the down-sampling factors) afterwards has no effect on the sampler."""
 
-    def __init__(self, loader, batch_size, seed=0, filter_on_device=False):
+    def __init__(self, loader, batch_size, seed=0, filter_on_device=False, median_on_device=False):
         kind = loader.lres_filter if loader.lres_filter and loader.lres_filter != 'none' else None
         if kind and not filter_on_device:
             raise NotImplementedError("DeviceBatchSampler does not filter (lres_filter=%r): RB2DeviceLoader.get() is the path "
                                       "that applies the low-res filters (filter_on_device=True filters gaussian / uniform / "
                                       "maximum in the sampler)" % (kind,))
-        if kind and kind not in ('gaussian', 'uniform', 'maximum'):
+        if kind and kind not in ('gaussian', 'uniform', 'maximum') and not (kind == 'median' and median_on_device):
             raise NotImplementedError("DeviceBatchSampler(filter_on_device=True) has no kernel for lres_filter=%r (gaussian / "
-                                      "uniform / maximum are built): RB2DeviceLoader.get() is the path that applies it"
-                                      % (kind,))
+                                      "uniform / maximum are built): RB2DeviceLoader.get() is the path that applies it%s"
+                                      % (kind, ", or pass median_on_device=True" if kind == 'median' else ""))
+        if kind == 'median':
+            from ._lib import FILTER_MEDIAN_MAX_RADIUS as rmax
+            if max(loader.downsamp_t, loader.downsamp_xz) - 1 > rmax:
+                raise NotImplementedError("DeviceBatchSampler(median_on_device=True): window radius downsamp - 1 = %d above the "
+                                          "limit of %d (downsamp_t = %d, downsamp_xz = %d; at most %d)"
+                                          % (max(loader.downsamp_t, loader.downsamp_xz) - 1, rmax, loader.downsamp_t,
+                                             loader.downsamp_xz, rmax + 1))
         if int(batch_size) <= 0:
             raise ValueError("batch_size must be positive")
         if not loader.data_cl.is_cuda:
@@ -354,8 +404,8 @@ class DeviceBatchSampler:
             f.T, f.Z, f.X = d.T, d.Z, d.X
             f.nt, f.nz, f.nx = n
             f.rt, f.rz, f.rx = loader._ranges
-            f.B, f.kind = B, _lib.FILTER_KINDS[kind]
-            if kind == 'maximum':
+            f.B, f.kind = B, _lib.FILTER_MEDIAN if kind == 'median' else _lib.FILTER_KINDS[kind]
+            if kind in ('maximum', 'median'):
                 self._weights = [None, None, None]
                 radii = (loader.downsamp_t - 1, loader.downsamp_xz - 1, loader.downsamp_xz - 1)      # window 2 ds - 1
             else:
@@ -367,7 +417,10 @@ class DeviceBatchSampler:
                 f.r[k] = radii[k]
                 f.nw[k] = 0 if self._weights[k] is None else self._weights[k].numel()
             self._fdesc = f
-            self._scratch = (torch.zeros(B, *n, 4, device=dev), torch.zeros(B, *n, 4, device=dev))     # ping-pong crops
+            if kind == 'median':
+                self._scratch = (torch.zeros(B, *n, 4, device=dev),)                                   # ONE crop: no ping-pong
+            else:
+                self._scratch = (torch.zeros(B, *n, 4, device=dev), torch.zeros(B, *n, 4, device=dev))     # ping-pong crops
         self.seed(seed)
 
     def __len__(self):
@@ -413,10 +466,16 @@ class DeviceBatchSampler:
         import ctypes as C
         from . import _lib
         if self.filter:
-            w, (sa, sb) = self._weights, self._scratch
-            _lib.check(_lib.lib().stpde_sampler_filter(
-                C.byref(self._fdesc), _lib.ptr(self._state), _lib.ptr(self.loader.data_cl), _lib.ptr(crop_idx), _lib.ptr(w[0]),
-                _lib.ptr(w[1]), _lib.ptr(w[2]), _lib.ptr(sa), _lib.ptr(sb), _lib.stream_ptr()))
+            sa = self._scratch[0]
+            if self.filter == 'median':
+                _lib.check(_lib.lib().stpde_sampler_median(
+                    C.byref(self._fdesc), _lib.ptr(self._state), _lib.ptr(self.loader.data_cl), _lib.ptr(crop_idx), _lib.ptr(sa),
+                    _lib.stream_ptr()))
+            else:
+                w, sb = self._weights, self._scratch[1]
+                _lib.check(_lib.lib().stpde_sampler_filter(
+                    C.byref(self._fdesc), _lib.ptr(self._state), _lib.ptr(self.loader.data_cl), _lib.ptr(crop_idx),
+                    _lib.ptr(w[0]), _lib.ptr(w[1]), _lib.ptr(w[2]), _lib.ptr(sa), _lib.ptr(sb), _lib.stream_ptr()))
             _lib.check(_lib.lib().stpde_sampler_produce_filtered(
                 C.byref(self._desc), _lib.ptr(sa), _lib.ptr(self._taps[0]), _lib.ptr(self._taps[1]), _lib.ptr(self._taps[2]),
                 _lib.ptr(point_coord), _lib.ptr(self.lres), _lib.ptr(self.point_value), _lib.stream_ptr()))
@@ -427,8 +486,8 @@ class DeviceBatchSampler:
             _lib.ptr(self.point_value), _lib.stream_ptr()))
 
     def draw(self):
-        """Next batch: two library calls on the current stream (three with a filter: draw, filter passes, produce from the
-        filtered crops), capturable, no allocation, no synchronisation.  Returns the
+        """Next batch: two library calls on the current stream (three with a filter: draw, filter passes or the median
+        selection, produce from the filtered crops), capturable, no allocation, no synchronisation.  Returns the
         static (lres [B,4,nt_l,nz_l,nx_l], point_coord [B,N,3], point_value [B,N,4]); ``crop_idx`` holds the ids."""
         import ctypes as C
         from . import _lib

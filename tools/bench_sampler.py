@@ -15,6 +15,11 @@ query points per crop; synthetic RB2 run [4, 200, 512, 128], normalised outputs)
 ``--lres-filter gaussian | uniform | maximum`` turns the reference's low-res pre-filter on in both loaders: ``get()`` then filters
 with composed torch ops per batch (``dataloader_spacetime.lres_filter``), ``draw()`` with the filter passes of csrc/sampler.hip
 (``DeviceBatchSampler(filter_on_device=True)``); results of such a run belong in ``profiles/sampler_filter.json``.
+``--lres-filter median`` does the same with the selection kernel of csrc/sampler_median.hip (``median_on_device=True``); results
+belong in ``profiles/sampler_median.json``.  ``get()`` unfolds every voxel's 7 x 7 x 7 window for it -- 14.4 GB per batch of 10, on
+which ``torch.median`` then sorts -- so the per-batch pair is timed at B = 10 only (B = 64 would materialise ~92 GB) and wants few
+batches per sample (``--batches 3 --batch-warmup 1``); ``get()`` is unchanged from before the kernel existed, so pair member ``get`` IS
+the only median path there was.
 
 Both members of a pair are timed alternately, so that drift of the box hits both alike.  Every sample and the medians go to
 ``--out`` (JSON); the last line printed is that JSON.  No target is attached to these numbers.
@@ -48,9 +53,10 @@ def main():
     ap.add_argument("--batches", type=int, default=200, help="batches per sample of the per-batch pair")
     ap.add_argument("--steps", type=int, default=200, help="iterations per sample of the per-iteration pair")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--batch-warmup", type=int, default=None, help="warm-up calls of the per-batch pair (default: --warmup)")
     ap.add_argument("--samples", type=int, default=3)
     ap.add_argument("--skip-iteration", action="store_true", help="only the per-batch pair")
-    ap.add_argument("--lres-filter", default="none", choices=["none", "gaussian", "uniform", "maximum"],
+    ap.add_argument("--lres-filter", default="none", choices=["none", "gaussian", "uniform", "maximum", "median"],
                     help="low-res pre-filter of both loaders (draw() then filters on the device)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -62,7 +68,7 @@ def main():
     from space_time_pde_amd.dataloader_spacetime import DeviceBatchSampler, RB2DeviceLoader
     from space_time_pde_amd.train_step import GraphedStep
 
-    def alternate(fa, fb, n, sync_each):
+    def alternate(fa, fb, n, sync_each, warmup=None):
         """samples of (ms per call of fa, of fb), timed alternately"""
         def timed(fn):
             torch.cuda.synchronize()
@@ -74,7 +80,7 @@ def main():
             torch.cuda.synchronize()
             return round(1e3 * (time.perf_counter() - t0) / n, 4)
         for fn in (fa, fb):
-            for _ in range(args.warmup):
+            for _ in range(args.warmup if warmup is None else warmup):
                 r = fn()
             torch.cuda.synchronize()
         gc.collect()
@@ -94,15 +100,16 @@ def main():
     ld = RB2DeviceLoader(data, nx=128, nz=128, nt=16, n_samp_pts_per_crop=1024, downsamp_xz=4, downsamp_t=4,
                          normalize_output=True, device=dev, lres_filter=args.lres_filter)
     on_device = args.lres_filter != "none"
-    for nb in (10, 64):
-        s = DeviceBatchSampler(ld, nb, seed=0, filter_on_device=on_device)
+    median = args.lres_filter == "median"
+    for nb in ((10,) if median else (10, 64)):
+        s = DeviceBatchSampler(ld, nb, seed=0, filter_on_device=on_device, median_on_device=median)
         gen = torch.Generator().manual_seed(nb)
 
         def get():
             idx = torch.randint(0, len(ld), (nb,), generator=gen).tolist()        # the host sampler's ids
             return ld.get(idx)[0]
 
-        sa, sb = alternate(get, lambda: s.draw()[0], args.batches, False)
+        sa, sb = alternate(get, lambda: s.draw()[0], args.batches, False, args.batch_warmup)
         out["per_batch"]["B=%d" % nb] = {
             "crop": "16x128x128 -> 4x32x32 low-res + 1024 target points", "batches_per_sample": args.batches,
             "get_ms": sa, "draw_ms": sb, "median_get_ms": statistics.median(sa), "median_draw_ms": statistics.median(sb),
@@ -134,7 +141,7 @@ def main():
         unet_b, net_b = copy.deepcopy(unet), copy.deepcopy(net)
         opt_b = optim.FusedClipAdam(list(unet_b.parameters()) + list(net_b.parameters()), lr=1e-2, clip_grad=1.0, flat=False,
                                     capturable=True)
-        s = DeviceBatchSampler(ld, B, seed=0, filter_on_device=on_device)
+        s = DeviceBatchSampler(ld, B, seed=0, filter_on_device=on_device, median_on_device=median)
         gstep_b = GraphedStep(unet_b, net_b, physics.get_rb2_pde_layer(**RB2), None, None, None, N, ALPHA_REG, ALPHA_PDE, "l1",
                               optimizer=opt_b, sampler=s)
         assert lig.stats["hip_jet_calls"] > n0, "HIP jet path was not taken"

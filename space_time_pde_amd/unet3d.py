@@ -19,8 +19,10 @@ fp32.  The mode is read once per autograd node at forward time, so its backward 
 stay fp32 whatever the mode.
 """
 import ctypes as C
+import dataclasses
 import math
 import os
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -120,8 +122,9 @@ def _bf16():
 
 
 def _desc(x, ci, co, k, bf=0, det=None):
+    """stpde_conv3d_desc of a convolution over x [B,T,Z,X,...] (a tensor, or its shape)"""
     d = _lib.Conv3dDesc()
-    d.B, d.T, d.Z, d.X = x.shape[0], x.shape[1], x.shape[2], x.shape[3]
+    d.B, d.T, d.Z, d.X = tuple(getattr(x, "shape", x))[:4]
     d.Ci, d.Co, d.ksize = ci, co, k
     d.det = _det() if det is None else det      # (None: a forward-time caller that takes its own reading; every autograd
     #                                             node passes the ctx.det of its forward)
@@ -129,6 +132,21 @@ def _desc(x, ci, co, k, bf=0, det=None):
     return d
 
 
+def _fused_args(shape, ci, co, k, bf, det):
+    """stpde_conv3d_fused_args with its descriptor filled in and every pointer NULL"""
+    a = _lib.Conv3dFusedArgs()
+    a.d = _desc(shape, ci, co, k, bf, det)
+    return a
+
+
+def _bn_desc(n, c, training, relu, eps, momentum, det, scratch_zeroed, stats_mode=0, reduce_done=0):
+    d = _lib.BnDesc()
+    d.N, d.C, d.training, d.relu, d.eps, d.momentum = n, c, int(training), int(relu), eps, momentum
+    d.det, d.scratch_zeroed, d.stats_mode, d.reduce_done = det, int(scratch_zeroed), stats_mode, int(reduce_done)
+    return d
+
+
+_ptr = _lib.ptr      # (None -> NULL)
 _side_streams = {}
 
 
@@ -152,8 +170,8 @@ class _DeferredGrads:
     most of the chip idle; the weight-gradient kernels fill it.  Only ``loss.backward()`` sees the gradients (they are
     accumulated into ``.grad``); ``torch.autograd.grad(..., unet.parameters())`` does not -- hence opt-in."""
 
-    def __init__(self, convs, dwall, sizes, device, det):
-        self.convs, self.dwall, self.device = convs, dwall, device
+    def __init__(self, convs, dwall, uidx, device, det):
+        self.convs, self.dwall, self.uidx, self.device = convs, dwall, uidx, device
         self.side = _side_stream(device)
         nb = [c.weight.shape[0] if c.bias is not None else 0 for c in convs]
         self.nbias = max(1, sum(nb))
@@ -168,11 +186,18 @@ class _DeferredGrads:
     def bias_slice(self, i):
         return self.dball[self.acc_w * int(self.boff[i]):self.acc_w * int(self.boff[i + 1])]
 
-    def enqueue(self, i):
+    def on_side(self, i, ready, operands):
+        """``with`` this: the gradient kernels of convolution i go to the side stream, behind the event ``ready`` on the
+        stream that produced their operands (not behind the input-gradient kernels queued after it: the two run side by
+        side).  The operands stay referenced until the callback has made the main stream wait for the side stream: no
+        record_stream(), whose event-polled block reuse makes the caching allocator's behaviour timing-dependent."""
+        self.keep.append(operands)
+        self.side.wait_event(ready)
         self.used.add(i)
         if not self.queued:
             self.queued = True
             torch.autograd.Variable._execution_engine.queue_callback(self.finalize)
+        return torch.cuda.stream(self.side)
 
     @staticmethod
     def unpack_index(convs, sizes, device):
@@ -213,43 +238,83 @@ class _DeferredGrads:
         self.used = set()
 
 
+class _ConvStep(NamedTuple):
+    """What one convolution's autograd node needs from the step it runs in.  ``UNet3d._prepare_step`` makes one per
+    convolution (all packs from one gather, the gradient destinations slices of one buffer); ``alone`` makes the record of
+    a convolution that no step serves."""
+    fpack: torch.Tensor                  # A-operand pack of the forward convolution
+    bpack: torch.Tensor                  # ... of the input-gradient convolution (transposed, taps flipped)
+    dw: Optional[torch.Tensor]           # zero-filled weight-gradient destination, sized for ``det``; None: allocate one
+    det: int                             # deterministic mode, read once: by the step, or by the node for ``alone``
+    defer: Optional[_DeferredGrads]      # not None: weight / bias gradients go to its buffers, on its side stream
+    index: int                           # of this convolution in ``defer``
+
+    @classmethod
+    def alone(cls, weight, device, det):
+        fidx, bidx, _, _ = _pack_indices(weight.shape[0], weight.shape[1], weight.shape[2], device)
+        wflat = torch.cat([weight.detach().reshape(-1), weight.new_zeros(1)])
+        return cls(wflat[fidx], wflat[bidx], None, det, None, -1)
+
+
+def _weight_grads(cs, dwt, d, x, gy, ready, ci, want_w, want_b, onload=None):
+    """Weight (+ bias) gradient of the convolution ``d`` from its input x (channels padded to d.Ci) and output gradient gy:
+    one kernel, the bias gradient = column sums of gy out of the same pass.  dwt = ``cs.dw``, handed over by the node the
+    first time only (a second backward gets fresh accumulators); onload = (stat, gamma, beta) of the BatchNorm + ReLU to
+    apply to x on load.  Returns (dw [co, ci, k, k, k] if want_w, db if want_b) -- or (None, None) when the step defers
+    them: the kernel is on the side stream and ``.grad`` is assigned when the backward pass is over."""
+    L = _lib.lib()
+
+    def launch(dwt, dbt):
+        if onload is not None:
+            _lib.check(L.stpde_conv3d_wgrad_onload(C.byref(d), _ptr(x), _ptr(gy), _ptr(dwt), _ptr(dbt), _ptr(onload[0]),
+                                                   _ptr(onload[1]), _ptr(onload[2]), _lib.stream_ptr()))
+        else:
+            _lib.check(L.stpde_conv3d_wgrad_bias(C.byref(d), _ptr(x), _ptr(gy), _ptr(dwt), _ptr(dbt), _lib.stream_ptr()))
+
+    if cs.defer is not None and dwt is not None:
+        with cs.defer.on_side(cs.index, ready, (gy, x) + tuple(onload or ())):
+            launch(dwt, cs.defer.bias_slice(cs.index) if want_b else None)     # (dball is zero-filled per step)
+        return None, None
+    ntap, co, cip = d.ksize ** 3, d.Co, d.Ci
+    if dwt is None:
+        dwt = _acc_zeros(ntap * co * cip, gy.device, cs.det)
+    dbt = _acc_zeros(co, gy.device, cs.det) if want_b else None
+    launch(dwt, dbt)
+    dwt = _acc_value(dwt, ntap * co * cip, cs.det).view(ntap, co, cip)     # (deterministic mode: long accumulators -> fp32)
+    if dbt is not None:
+        dbt = _acc_value(dbt, co, cs.det)
+    dw = dwt[:, :, :ci].permute(1, 2, 0).reshape((co, ci) + (d.ksize,) * 3) if want_w else None
+    return dw, dbt
+
+
 class _Conv3dHip(torch.autograd.Function):
     """y = conv3d(x, weight, bias), stride 1, padding (k-1)/2, on channels-last x [B,T,Z,X,Ci].
 
-    packs = (forward A-operand pack, input-gradient pack) prepared by the caller (UNet3d packs all of its convolutions
-    with one gather per step), or None: packed here."""
+    step = the _ConvStep of this convolution in the U-Net step that calls it, or None: made here."""
 
     @staticmethod
     @_lib.guarded
-    def forward(ctx, x, weight, bias, packs=None):
+    def forward(ctx, x, weight, bias, step=None):
         L = _lib.lib()
         co, ci, k = weight.shape[0], weight.shape[1], weight.shape[2]
         cip, cop = (ci + 15) // 16 * 16, (co + 15) // 16 * 16
         if cop != co:
             raise NotImplementedError("HIP conv3d needs out_channels to be a multiple of 16 (got %d)" % co)
-        ctx.dwbuf = ctx.defer = None
-        if packs is None:
-            ctx.det = _det()                    # deterministic mode of this node: its backward uses the same
-            fidx, bidx, _, _ = _pack_indices(co, ci, k, x.device)
-            wflat = torch.cat([weight.detach().reshape(-1), weight.new_zeros(1)])
-            fpack, bpack = wflat[fidx], None
-        else:
-            fpack, bpack, ctx.dwbuf, ctx.det = packs[:4]      # (the mode: the step's reading, as dwbuf was sized)
-            if len(packs) > 4:
-                ctx.defer = packs[4:6]              # (_DeferredGrads, index of this convolution in it)
-            wflat = bidx = None
+        # (the deterministic mode of this node, forward and backward: the step's reading, as its dw was sized, or its own)
+        ctx.step = step = step if step is not None else _ConvStep.alone(weight, x.device, _det())
+        ctx.dwbuf = step.dw
         xin = x.detach()
         if cip != ci:
             xin = F.pad(xin, (0, cip - ci))
         xin = xin.contiguous()
         y = torch.empty(x.shape[:-1] + (co,), device=x.device, dtype=torch.float32)
         ctx.bf = _bf16() if k == 3 else 0       # operand mode of this node: its backward uses the same
-        d = _desc(xin, cip, co, k, ctx.bf, ctx.det)
-        _lib.check(L.stpde_conv3d_fwd(C.byref(d), _lib.ptr(xin), _lib.ptr(fpack),
+        d = _desc(xin, cip, co, k, ctx.bf, step.det)
+        _lib.check(L.stpde_conv3d_fwd(C.byref(d), _lib.ptr(xin), _lib.ptr(step.fpack),
                                       _lib.ptr(bias.detach().contiguous()) if bias is not None else None,
                                       _lib.ptr(y), _lib.stream_ptr()))
-        ctx.save_for_backward(xin, wflat if bpack is None else bpack)
-        ctx.meta = (co, ci, k, cip, bidx, bias is not None)
+        ctx.save_for_backward(xin, step.bpack)
+        ctx.meta = (co, ci, k, cip, bias is not None)
         return y
 
     @staticmethod
@@ -257,53 +322,26 @@ class _Conv3dHip(torch.autograd.Function):
     @_lib.guarded
     def backward(ctx, gy):
         L = _lib.lib()
-        xin, wsaved = ctx.saved_tensors
-        co, ci, k, cip, bidx, has_bias = ctx.meta
+        xin, bpack = ctx.saved_tensors
+        co, ci, k, cip, has_bias = ctx.meta
+        cs = ctx.step
         gy = gy.contiguous()
         dx = dw = db = None
-        ready = torch.cuda.current_stream().record_event() if ctx.defer is not None else None   # gy is complete here
+        ready = torch.cuda.current_stream().record_event() if cs.defer is not None else None   # gy is complete here
         if ctx.needs_input_grad[0]:
             dxp = torch.empty(xin.shape, device=gy.device, dtype=torch.float32)
-            d = _desc(gy, co, cip, k, ctx.bf, ctx.det)
-            bpack = wsaved if bidx is None else wsaved[bidx]
+            d = _desc(gy, co, cip, k, ctx.bf, cs.det)
             _lib.check(L.stpde_conv3d_fwd(C.byref(d), _lib.ptr(gy), _lib.ptr(bpack), None, _lib.ptr(dxp),
                                           _lib.stream_ptr()))
             dx = dxp[..., :ci] if cip != ci else dxp
-        if ctx.defer is not None and ctx.dwbuf is not None:
-            # weight gradient + bias reduction on the side stream; .grad is assigned when the backward pass is over
-            defer, idx = ctx.defer
-            # the operands stay referenced until the callback has made the main stream wait for the side stream: no
-            # record_stream(), whose event-polled block reuse makes the caching allocator's behaviour timing-dependent
-            defer.keep.append((gy, xin))
-            defer.side.wait_event(ready)          # not the input-gradient kernel just queued: the two run side by side
-            with torch.cuda.stream(defer.side):
-                want_b = has_bias and ctx.needs_input_grad[2]
-                if ctx.needs_input_grad[1]:
-                    # (the bias gradient = column sums of gy comes out of the same kernel: dball is zero-filled per step)
-                    dwt, ctx.dwbuf = ctx.dwbuf, None
-                    d = _desc(xin, cip, co, k, ctx.bf, ctx.det)
-                    _lib.check(L.stpde_conv3d_wgrad_bias(C.byref(d), _lib.ptr(xin), _lib.ptr(gy), _lib.ptr(dwt),
-                                                         _lib.ptr(defer.bias_slice(idx)) if want_b else None,
-                                                         _lib.stream_ptr()))
-                elif want_b:
-                    defer.direct_bias[idx] = gy.reshape(-1, co).sum(0)     # (a plain torch reduction: no atomics)
-            defer.enqueue(idx)
-            return dx, None, None, None
+        want_b = has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
-            ntap = k ** 3
-            dwt, ctx.dwbuf = ctx.dwbuf, None     # zero-filled slice of the per-step buffer (used once), else a fresh one
-            if dwt is None:
-                dwt = _acc_zeros(ntap * co * cip, gy.device, ctx.det)
-            d = _desc(xin, cip, co, k, ctx.bf, ctx.det)
-            if has_bias and ctx.needs_input_grad[2]:
-                db = _acc_zeros(co, gy.device, ctx.det)     # column sums of gy, from the same kernel
-            _lib.check(L.stpde_conv3d_wgrad_bias(C.byref(d), _lib.ptr(xin), _lib.ptr(gy), _lib.ptr(dwt), _lib.ptr(db),
-                                                 _lib.stream_ptr()))
-            dwt = _acc_value(dwt, ntap * co * cip, ctx.det).view(ntap, co, cip)     # (deterministic mode: long accumulators -> fp32)
-            if db is not None:
-                db = _acc_value(db, co, ctx.det)
-            dw = dwt[:, :, :ci].permute(1, 2, 0).reshape(co, ci, k, k, k)
-        if has_bias and ctx.needs_input_grad[2] and db is None:
+            dwt, ctx.dwbuf = ctx.dwbuf, None     # the step's slice, used once
+            dw, db = _weight_grads(cs, dwt, _desc(xin, cip, co, k, ctx.bf, cs.det), xin, gy, ready, ci, True, want_b)
+        elif want_b and cs.defer is not None and ctx.dwbuf is not None:      # frozen weight, deferred gradients
+            with cs.defer.on_side(cs.index, ready, (gy,)):
+                cs.defer.direct_bias[cs.index] = gy.reshape(-1, co).sum(0)     # (a plain torch reduction: no atomics)
+        elif want_b:
             db = gy.reshape(-1, co).sum(0)
         return dx, dw, db, None
 
@@ -321,10 +359,11 @@ def _hip_conv_ok(x, conv):
             and (conv.bias is None or conv.bias.dtype == torch.float32))
 
 
-def _conv_cl(x, conv):
-    """Apply an nn.Conv3d (1x1x1 or 3x3x3/pad 1, stride 1) to a channels-last tensor [B,T,Z,X,C]."""
+def _conv_cl(x, conv, step=None):
+    """Apply an nn.Conv3d (1x1x1 or 3x3x3/pad 1, stride 1) to a channels-last tensor [B,T,Z,X,C]; step: the _UNetStep
+    this call is part of, if any."""
     if _hip_conv_ok(x, conv):
-        return _Conv3dHip.apply(x, conv.weight, conv.bias, getattr(conv, "_stpde_packs", None))
+        return _Conv3dHip.apply(x, conv.weight, conv.bias, step.convs.get(conv) if step is not None else None)
     y = conv(x.permute(0, 4, 1, 2, 3))
     return y.permute(0, 2, 3, 4, 1).contiguous()
 
@@ -345,12 +384,19 @@ class _ContiguousGrad(torch.autograd.Function):
         return g.contiguous()
 
 
-def _bn_cl(x, bn):
+def _count_batch(bns, step):
+    """num_batches_tracked += 1 of the BatchNorms a call runs in training mode -- unless its step has done that already"""
+    if step is not None and step.counted:
+        return
+    for bn in bns:
+        if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+
+
+def _bn_cl(x, bn, step=None):
     """nn.BatchNorm3d semantics (batch statistics in training, running-stat update) on channels-last data."""
     shp = x.shape
-    if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None \
-            and not getattr(bn, "_stpde_counted", False):
-        bn.num_batches_tracked.add_(1)
+    _count_batch((bn,), step)
     y = F.batch_norm(x.reshape(-1, shp[-1]), bn.running_mean, bn.running_var, bn.weight, bn.bias,
                      bn.training or not bn.track_running_stats, bn.momentum, bn.eps)
     return y.reshape(shp)
@@ -362,20 +408,18 @@ class _BnActHip(torch.autograd.Function):
 
     @staticmethod
     @_lib.guarded
-    def forward(ctx, x, residual, weight, bias, running_mean, running_var, training, momentum, eps, relu, scratch=None):
+    def forward(ctx, x, residual, weight, bias, running_mean, running_var, training, momentum, eps, relu, scratch=None,
+                det=None):
         L = _lib.lib()
         x = x.contiguous()
         residual = residual.contiguous() if residual is not None else None
         c = x.shape[-1]
-        d = _lib.BnDesc()
-        d.N, d.C, d.training, d.relu, d.eps, d.momentum = x.numel() // c, c, int(training), int(relu), eps, momentum
         # scratch = zero-filled [BN_REP][6][C] slice of the U-Net's per-step buffer (forward + backward sums): no memsets
         ctx.scratch = scratch
-        d.scratch_zeroed = int(scratch is not None)
+        ctx.det = _det() if det is None else det      # (det: the reading of the step that serves this call)
+        # deterministic mode: statistics in the double format as long accumulators (stats_mode 1: the first 4RC floats)
+        d = _bn_desc(x.numel() // c, c, training, relu, eps, momentum, ctx.det, scratch is not None, stats_mode=ctx.det)
         R = _lib.BN_REP
-        ctx.det = _det()
-        if ctx.det:     # deterministic mode: statistics in the double format as long accumulators (the first 4RC floats)
-            d.det, d.stats_mode = 1, 1
         sums = (scratch[:4 * R * c] if scratch is not None else torch.empty(4 * R * c, device=x.device)) if training else None
         # (scratch layout, shared with _ResBlockHip: [0 : 4RC] forward sums -- this path's float format takes the first 3RC --,
         # [4RC : 6RC] backward sums)
@@ -397,9 +441,8 @@ class _BnActHip(torch.autograd.Function):
     def backward(ctx, gy):
         L = _lib.lib()
         x, y, weight, stat = ctx.saved_tensors
-        d = _lib.BnDesc()
-        d.N, d.C, d.training, d.relu, d.eps, d.momentum = ctx.desc
-        d.det = ctx.det
+        scratch, ctx.scratch = ctx.scratch, None          # used once (a second backward gets a fresh buffer + memset)
+        d = _bn_desc(*ctx.desc, ctx.det, scratch is not None)
         c = d.C
         gy = gy.contiguous()
         need_x, need_r, need_w, need_b = ctx.needs_input_grad[:4]
@@ -407,42 +450,35 @@ class _BnActHip(torch.autograd.Function):
         dr = torch.empty_like(x) if (ctx.has_res and need_r) else None
         dw = torch.empty(c, device=x.device) if (weight is not None and need_w) else None
         db = torch.empty(c, device=x.device) if need_b else None
-        scratch, ctx.scratch = ctx.scratch, None          # used once (a second backward gets a fresh buffer + memset)
-        d.scratch_zeroed = int(scratch is not None)
         R = _lib.BN_REP
         bsum = scratch[4 * R * c:] if scratch is not None else torch.empty(2 * R * c, device=x.device)
         _lib.check(L.stpde_bn_bwd(C.byref(d), _lib.ptr(x), _lib.ptr(y), _lib.ptr(gy),
                                   _lib.ptr(weight.detach() if weight is not None else None), _lib.ptr(stat),
                                   _lib.ptr(bsum), _lib.ptr(dx), _lib.ptr(dr), _lib.ptr(dw), _lib.ptr(db),
                                   _lib.stream_ptr()))
-        return dx, dr, dw, db, None, None, None, None, None, None, None
+        return dx, dr, dw, db, None, None, None, None, None, None, None, None
 
 
-def _bn_act(x, bn, relu, residual=None):
+def _bn_act(x, bn, relu, residual=None, step=None):
     """act(bn(x) [+ residual]) with nn.BatchNorm3d semantics on channels-last data: the HIP kernels on CUDA tensors,
-    torch ops otherwise (CPU, exotic BatchNorm configurations)."""
+    torch ops otherwise (CPU, exotic BatchNorm configurations); step: the _UNetStep this call is part of, if any."""
     c = x.shape[-1]
     training = bn.training or not bn.track_running_stats
     hip = (x.is_cuda and x.dtype == torch.float32 and 16 <= c <= 512 and (c & (c - 1)) == 0
            and bn.momentum is not None and (training or bn.running_mean is not None)
            and (bn.weight is None) == (bn.bias is None))
     if not hip:
-        h = _bn_cl(x, bn)
+        h = _bn_cl(x, bn, step)
         if residual is not None:
             h = h + residual
         return F.relu(h) if relu else h
     if training and x.numel() // c == 1:   # same refusal as torch.nn.functional.batch_norm
         raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(tuple(x.shape)))
-    if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None \
-            and not getattr(bn, "_stpde_counted", False):
-        bn.num_batches_tracked.add_(1)
+    _count_batch((bn,), step)
     rm = bn.running_mean if bn.track_running_stats else None
     rv = bn.running_var if bn.track_running_stats else None
-    scratch = getattr(bn, "_stpde_scratch", None)
-    if scratch is not None:
-        bn._stpde_scratch = None              # one use per step
     return _BnActHip.apply(x, residual, bn.weight, bn.bias, rm, rv, training, float(bn.momentum), float(bn.eps),
-                           bool(relu), scratch)
+                           bool(relu), *((step.take_scratch(bn), step.det) if step is not None else ()))
 
 
 class _ResampleHip(torch.autograd.Function):
@@ -538,10 +574,6 @@ def _fused_ok(blk, x):
     return True
 
 
-def _ptr(t):
-    return _lib.ptr(t) if t is not None else None
-
-
 class _ResBlockHip(torch.autograd.Function):
     """One ResBlock3D (reference src/unet3d.py:39-56) in training mode as ONE autograd node over the fused kernels of
     csrc/conv3d_fused.hip (round 4):
@@ -557,7 +589,7 @@ class _ResBlockHip(torch.autograd.Function):
 
     @staticmethod
     @_lib.guarded
-    def forward(ctx, blk, x, w1, b1, w2, b2, w3, b3, ws, bs, g1, be1, g2, be2, g3, be3):
+    def forward(ctx, blk, x, w1, b1, w2, b2, w3, b3, ws, bs, g1, be1, g2, be2, g3, be3, step=None):
         L = _lib.lib()
         dev = x.device
         ci, cn, co = x.shape[-1], w1.shape[0], w3.shape[0]
@@ -569,56 +601,33 @@ class _ResBlockHip(torch.autograd.Function):
         shp = tuple(xin.shape[:4])
         N = shp[0] * shp[1] * shp[2] * shp[3]
         R = _lib.BN_REP
-        convs = (blk.conv1, blk.conv2, blk.conv3, blk.shortcut)
-        packs = []
-        det = _det()                          # ONE reading for the convolutions of this node that the step does not serve
-        for conv, w in zip(convs, (w1, w2, w3, ws)):
-            p = getattr(conv, "_stpde_packs", None)
-            if p is None:
-                fidx, bidx, _, _ = _pack_indices(w.shape[0], w.shape[1], w.shape[2], dev)
-                wflat = torch.cat([w.detach().reshape(-1), w.new_zeros(1)])
-                p = (wflat[fidx], wflat[bidx], None, det)
-            packs.append(p)
+        ctx.bf = _bf16()                      # operand mode of conv2 (3x3x3), for the forward and the backward of this node
+        # deterministic mode, likewise: ONE reading for the whole block -- the step's, as its buffers were sized, or this node's
+        ctx.det = det = step.det if step is not None else _det()
+        served = step.convs if step is not None else {}
+        ctx.steps = steps = [served.get(conv) or _ConvStep.alone(w, dev, det)
+                             for conv, w in zip((blk.conv1, blk.conv2, blk.conv3, blk.shortcut), (w1, w2, w3, ws))]
         bns = (blk.bn1, blk.bn2, blk.bn3)
         fsum, bsum, stat = [], [], []
         for bn in bns:
             c = bn.num_features
-            sc = getattr(bn, "_stpde_scratch", None)
-            if sc is not None:
-                bn._stpde_scratch = None              # one use per step
-            else:
+            sc = step.take_scratch(bn) if step is not None else None
+            if sc is None:
                 sc = torch.zeros(6 * R * c, device=dev)
             fsum.append(sc[:4 * R * c])
             bsum.append(sc[4 * R * c:])
             stat.append(torch.empty(2 * c, device=dev))
         rm = [bn.running_mean if bn.track_running_stats else None for bn in bns]
         rv = [bn.running_var if bn.track_running_stats else None for bn in bns]
-        ctx.bf = _bf16()                      # operand mode of conv2 (3x3x3), for the forward and the backward of this node
-        ctx.det = packs[0][3]                 # deterministic mode, likewise (the step's reading, or this node's own)
-        assert all(p[3] == ctx.det for p in packs), "one deterministic mode per residual block"
-
-        def conv_args(ci_, co_, k):
-            a = _lib.Conv3dFusedArgs()
-            a.d.B, a.d.T, a.d.Z, a.d.X = shp
-            a.d.Ci, a.d.Co, a.d.ksize = ci_, co_, k
-            a.d.det = ctx.det
-            a.d.mfma_bf16 = ctx.bf if k == 3 else 0
-            return a
-
-        def bn_desc(c, relu, bn):
-            d = _lib.BnDesc()
-            d.N, d.C, d.training, d.relu, d.eps, d.momentum = N, c, 1, int(relu), float(bn.eps), float(bn.momentum)
-            d.scratch_zeroed, d.stats_mode = 1, 2
-            d.det = ctx.det
-            return d
-
+        conv_args = lambda ci_, co_, k: _fused_args(shp, ci_, co_, k, ctx.bf, det)
+        bn_desc = lambda c, relu, bn: _bn_desc(N, c, 1, relu, float(bn.eps), float(bn.momentum), det, 1, stats_mode=2)
         st = _lib.stream_ptr()
         new = lambda c: torch.empty(shp + (c,), device=dev, dtype=torch.float32)
         # conv1 + shortcut: one pass over x, bn1's statistics from conv1's accumulator tiles
         y1, sc_out = new(cn), new(co)
         a = conv_args(cip, cn, 1)
-        a.x, a.w_pack, a.bias, a.y = _ptr(xin), _ptr(packs[0][0]), _ptr(b1.detach() if b1 is not None else None), _ptr(y1)
-        a.y2, a.wo2_pack, a.bias2, a.Co2 = _ptr(sc_out), _ptr(packs[3][0]), _ptr(bs.detach() if bs is not None else None), co
+        a.x, a.w_pack, a.bias, a.y = _ptr(xin), _ptr(steps[0].fpack), _ptr(b1.detach() if b1 is not None else None), _ptr(y1)
+        a.y2, a.wo2_pack, a.bias2, a.Co2 = _ptr(sc_out), _ptr(steps[3].fpack), _ptr(bs.detach() if bs is not None else None), co
         a.out_sums = _ptr(fsum[0])
         _lib.check(L.stpde_conv3d_fused(C.byref(a), None, st))
         # bn1 + relu (elementwise pass only)
@@ -630,13 +639,13 @@ class _ResBlockHip(torch.autograd.Function):
         # conv2 (+ bn2 statistics)
         y2 = new(cn)
         a = conv_args(cn, cn, 3)
-        a.x, a.w_pack, a.bias, a.y = _ptr(h1), _ptr(packs[1][0]), _ptr(b2.detach() if b2 is not None else None), _ptr(y2)
+        a.x, a.w_pack, a.bias, a.y = _ptr(h1), _ptr(steps[1].fpack), _ptr(b2.detach() if b2 is not None else None), _ptr(y2)
         a.out_sums = _ptr(fsum[1])
         _lib.check(L.stpde_conv3d_fused(C.byref(a), None, st))
         # conv3 of relu(bn2(y2)) applied on load (+ bn3 statistics)
         y3 = new(co)
         a = conv_args(cn, co, 1)
-        a.x, a.w_pack, a.bias, a.y = _ptr(y2), _ptr(packs[2][0]), _ptr(b3.detach() if b3 is not None else None), _ptr(y3)
+        a.x, a.w_pack, a.bias, a.y = _ptr(y2), _ptr(steps[2].fpack), _ptr(b3.detach() if b3 is not None else None), _ptr(y3)
         a.in_sums, a.in_gamma, a.in_beta = _ptr(fsum[1]), _ptr(g2.detach() if g2 is not None else None), \
             _ptr(be2.detach() if be2 is not None else None)
         a.in_running_mean, a.in_running_var, a.in_stat = _ptr(rm[1]), _ptr(rv[1]), _ptr(stat[1])
@@ -650,11 +659,11 @@ class _ResBlockHip(torch.autograd.Function):
                                   _ptr(be3.detach() if be3 is not None else None), _ptr(rm[2]), _ptr(rv[2]),
                                   _ptr(fsum[2]), _ptr(stat[2]), _ptr(out), st))
         ctx.save_for_backward(xin, y1, h1, y2, y3, out if blk.final_relu else None, stat[0], stat[1], stat[2],
-                              g1, be1, g2, be2, g3, packs[0][1], packs[1][1], packs[2][1], packs[3][1])
+                              g1, be1, g2, be2, g3, *(cs.bpack for cs in steps))
         ctx.meta = (shp, N, ci, cip, cn, co, bool(blk.final_relu), [float(bn.eps) for bn in bns],
                     [float(bn.momentum) for bn in bns], (b1 is not None, b2 is not None, b3 is not None, bs is not None))
         ctx.bsum = bsum
-        ctx.dw = [(p[2], p[4:6] if len(p) > 4 else None) for p in packs]
+        ctx.dw = [cs.dw for cs in steps]      # the step's zero-filled slices, each used once
         stats["fused_resblocks"] += 1
         return out
 
@@ -675,23 +684,9 @@ class _ResBlockHip(torch.autograd.Function):
         st = _lib.stream_ptr()
         new = lambda c: torch.empty(shp + (c,), device=dev, dtype=torch.float32)
         vec = lambda t, c: torch.empty(c, device=dev) if t is not None else None
-
-        def conv_args(ci_, co_, k):
-            a = _lib.Conv3dFusedArgs()
-            a.d.B, a.d.T, a.d.Z, a.d.X = shp
-            a.d.Ci, a.d.Co, a.d.ksize = ci_, co_, k
-            a.d.det = ctx.det
-            a.d.mfma_bf16 = ctx.bf if k == 3 else 0
-            return a
-
-        def bn_desc(c, relu, k, reduce_done):
-            d = _lib.BnDesc()
-            d.N, d.C, d.training, d.relu, d.eps, d.momentum = N, c, 1, int(relu), eps[k], mom[k]
-            d.scratch_zeroed, d.reduce_done = int(zeroed), int(reduce_done)
-            d.det = ctx.det
-            return d
-
-        defer = ctx.dw[0][1][0] if ctx.dw[0][1] else None
+        conv_args = lambda ci_, co_, k: _fused_args(shp, ci_, co_, k, ctx.bf, ctx.det)
+        bn_desc = lambda c, relu, k, done: _bn_desc(N, c, 1, relu, eps[k], mom[k], ctx.det, zeroed, reduce_done=done)
+        defer = ctx.steps[0].defer
         # bn3 backward (reduction + elementwise): gradient of conv3's output and of the shortcut branch
         dy3, dsc = new(co), new(co)
         dg3, db3 = vec(g3, co), vec(g3, co)
@@ -743,58 +738,52 @@ class _ResBlockHip(torch.autograd.Function):
             a.x2, a.w2_pack, a.Ci2 = _ptr(dsc), _ptr(bps), co
             _lib.check(L.stpde_conv3d_fused(C.byref(a), None, st))
             dx = dxp[..., :ci] if cip != ci else dxp
-        # weight (+ bias) gradients: (conv, input, output gradient, kernel size, channels, on-load transform of the input)
-        jobs = [(2, y2, dy3, 1, cn, co, ev3, True), (3, xin, dsc, 1, cip, co, ev3, False),
-                (1, h1, dy2, 3, cn, cn, ev2, False), (0, xin, dy1, 1, cip, cn, ev1, False)]
-        # per convolution: its weight gradient (inputs 2, 4, 6, 8) or its bias gradient (3, 5, 7, 9) is wanted -- a block with
-        # frozen weights and trainable biases still gets its bias gradients (the kernel produces both from one pass)
-        need = [ctx.needs_input_grad[2 + 2 * k] or (has_b[k] and ctx.needs_input_grad[3 + 2 * k]) for k in range(4)]
+        # weight (+ bias) gradients: (conv, input, output gradient, kernel size, channels of the input: padded and not, of the
+        # output, event after which the operands are complete, on-load transform of the input)
+        jobs = [(2, y2, dy3, 1, cn, cn, co, ev3, (st2, g2, be2)), (3, xin, dsc, 1, cip, ci, co, ev3, None),
+                (1, h1, dy2, 3, cn, cn, cn, ev2, None), (0, xin, dy1, 1, cip, ci, cn, ev1, None)]
         gw = [None] * 4
         gb = [None] * 4
-        for k, xi, gy, ks, ci_, co_, ev, onload in jobs:
-            if not need[k]:
+        for k, xi, gy, ks, cip_, ci_, co_, ev, onload in jobs:
+            # its weight gradient (inputs 2, 4, 6, 8) or its bias gradient (3, 5, 7, 9) is wanted -- a block with frozen weights
+            # and trainable biases still gets its bias gradients (the kernel produces both from one pass)
+            want_w, want_b = ctx.needs_input_grad[2 + 2 * k], has_b[k] and ctx.needs_input_grad[3 + 2 * k]
+            if not (want_w or want_b):
                 continue
-            dwt, dfr = ctx.dw[k]
-            ctx.dw[k] = (None, dfr)                     # the zero-filled slice of the per-step buffer is used once
-            cd = _lib.Conv3dDesc()
-            cd.B, cd.T, cd.Z, cd.X = shp
-            cd.Ci, cd.Co, cd.ksize = ci_, co_, ks
-            cd.det = ctx.det
-            cd.mfma_bf16 = ctx.bf if ks == 3 else 0
-
-            def launch(dwt, dbt):
-                if onload:
-                    _lib.check(L.stpde_conv3d_wgrad_onload(C.byref(cd), _ptr(xi), _ptr(gy), _ptr(dwt), _ptr(dbt), _ptr(st2),
-                                                           _ptr(g2), _ptr(be2), _lib.stream_ptr()))
-                else:
-                    _lib.check(L.stpde_conv3d_wgrad_bias(C.byref(cd), _ptr(xi), _ptr(gy), _ptr(dwt), _ptr(dbt),
-                                                         _lib.stream_ptr()))
-
-            if dfr and dwt is not None:
-                dobj, idx = dfr
-                dobj.keep.append((gy, xi, st2, g2, be2))
-                dobj.side.wait_event(ev)
-                with torch.cuda.stream(dobj.side):
-                    launch(dwt, dobj.bias_slice(idx) if has_b[k] else None)
-                dobj.enqueue(idx)
-            else:
-                if dwt is None:
-                    dwt = _acc_zeros(ks ** 3 * co_ * ci_, dev, ctx.det)
-                dbt = _acc_zeros(co_, dev, ctx.det) if has_b[k] else None
-                launch(dwt, dbt)
-                dwt = _acc_value(dwt, ks ** 3 * co_ * ci_, ctx.det).view(ks ** 3, co_, ci_)     # (deterministic mode: -> fp32)
-                if dbt is not None:
-                    dbt = _acc_value(dbt, co_, ctx.det)
-                cin = ci if k in (0, 3) else ci_
-                if ctx.needs_input_grad[2 + 2 * k]:
-                    gw[k] = dwt[:, :, :cin].permute(1, 2, 0).reshape(co_, cin, ks, ks, ks)
-                gb[k] = dbt if ctx.needs_input_grad[3 + 2 * k] else None
+            dwt, ctx.dw[k] = ctx.dw[k], None
+            gw[k], dbt = _weight_grads(ctx.steps[k], dwt, _desc(shp, cip_, co_, ks, ctx.bf, ctx.det), xi, gy, ev, ci_, want_w,
+                                       has_b[k], onload)
+            gb[k] = dbt if want_b else None
         if _ResBlockHip.debug is not None:
             _ResBlockHip.debug.update(dy3=dy3, dsc=dsc, dz2=dz2, dy2=dy2, dz1=dz1, dy1=dy1, dx=dx, y1=y1, h1=h1, y2=y2, y3=y3,
                                       done=done.value)
-        return (None, dx, gw[0], gb[0], gw[1], gb[1], gw[2], gb[2], gw[3], gb[3], dg1, db1, dg2, db2, dg3, db3)
+        return (None, dx, gw[0], gb[0], gw[1], gb[1], gw[2], gb[2], gw[3], gb[3], dg1, db1, dg2, db2, dg3, db3, None)
 
     debug = None     # a dict here makes backward leave its intermediate gradients in it (tools/micro/dbg_resblock.py)
+
+
+@dataclasses.dataclass
+class _PackPlan:
+    """How UNet3d packs all of its convolutions at once on one device (built at the first step there)."""
+    device: str
+    index: torch.Tensor                    # gather index: concatenated weights (+ one zero) -> all packs, back to back
+    spans: list                            # per convolution: (start of fpack, start of bpack, end) in the gathered packs
+    uidx: Optional[torch.Tensor] = None    # deferred mode, built when first needed: _DeferredGrads.unpack_index
+
+
+@dataclasses.dataclass(frozen=True)
+class _UNetStep:
+    """Per-forward state of a UNet3d on the CUDA path (``UNet3d._prepare_step``), handed down explicitly to every block,
+    convolution and BatchNorm call of that forward."""
+    det: int              # THE reading of the deterministic mode of this step: every buffer below is sized for it
+    convs: dict           # nn.Conv3d -> its _ConvStep
+    scratch: dict         # nn.BatchNorm3d -> zero-filled [BN_REP][6][C] statistics scratch, until taken
+    counted: bool         # the step has bumped every num_batches_tracked: the calls it serves do not
+    defer: Optional[_DeferredGrads]
+
+    def take_scratch(self, bn):
+        """the scratch slice of bn -- once per step; after that None: the call brings its own (+ memset)"""
+        return self.scratch.pop(bn, None)
 
 
 class ResBlock3D(nn.Module):
@@ -814,21 +803,21 @@ class ResBlock3D(nn.Module):
         self.shortcut = nn.Conv3d(in_channels, out_channels, kernel_size=1, stride=1)
         self.final_relu = final_relu
 
-    def forward_cl(self, x):
-        """Channels-last in, channels-last out: conv1-bn1-relu-conv2-bn2-relu-conv3-bn3 + shortcut (+relu)."""
+    def forward_cl(self, x, step=None):
+        """Channels-last in, channels-last out: conv1-bn1-relu-conv2-bn2-relu-conv3-bn3 + shortcut (+relu).
+        step: the _UNetStep of the network forward this call is part of (None: a block on its own)."""
         if _fused_ok(self, x):
-            for bn in (self.bn1, self.bn2, self.bn3):
-                if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None \
-                        and not getattr(bn, "_stpde_counted", False):
-                    bn.num_batches_tracked.add_(1)
+            _count_batch((self.bn1, self.bn2, self.bn3), step)
             return _ResBlockHip.apply(self, x, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias,
                                       self.conv3.weight, self.conv3.bias, self.shortcut.weight, self.shortcut.bias,
                                       self.bn1.weight, self.bn1.bias, self.bn2.weight, self.bn2.bias,
-                                      self.bn3.weight, self.bn3.bias)
-        h = _bn_act(_conv_cl(x, self.conv1), self.bn1, True)
-        h = _bn_act(_conv_cl(h, self.conv2), self.bn2, True)
+                                      self.bn3.weight, self.bn3.bias, step)
+        # (a step is handed on only where there is one: a block on its own calls the layer helpers as any outside caller does)
+        kw = {"step": step} if step is not None else {}
+        h = _bn_act(_conv_cl(x, self.conv1, **kw), self.bn1, True, **kw)
+        h = _bn_act(_conv_cl(h, self.conv2, **kw), self.bn2, True, **kw)
         # bn3 + shortcut + final ReLU in one pass
-        return _bn_act(_conv_cl(h, self.conv3), self.bn3, self.final_relu, residual=_conv_cl(x, self.shortcut))
+        return _bn_act(_conv_cl(h, self.conv3, **kw), self.bn3, self.final_relu, residual=_conv_cl(x, self.shortcut, **kw), **kw)
 
     def forward(self, x):  # [B, C, T, Z, X] -> [B, C', T, Z, X] (channels-last view)
         h = self.forward_cl(x.permute(0, 2, 3, 4, 1).contiguous())
@@ -839,6 +828,7 @@ class ResBlock3D(nn.Module):
 
 class UNet3d(nn.Module):  # pylint: disable=too-many-instance-attributes
     """3D U-Net with residual blocks (reference :59-240)."""
+    _pack_plan = None      # the _PackPlan of the device the last step ran on
 
     def __init__(self, in_features=4, out_features=32, igres=(4, 32, 32), ogres=None, nf=16, mf=512):
         super().__init__()
@@ -929,12 +919,14 @@ class UNet3d(nn.Module):  # pylint: disable=too-many-instance-attributes
         self.up_interps = nn.ModuleList(up_interps)
 
     def _prepare_step(self, device):
-        """CUDA path: pack the weights of ALL convolutions with one concatenation + one index gather (instead of two
-        small kernels per convolution per pass) and bump all BatchNorm step counters with one foreach op."""
+        """CUDA path: the _UNetStep of one forward -- pack the weights of ALL convolutions with one concatenation + one index
+        gather (instead of two small kernels per convolution per pass) and bump all BatchNorm step counters with one foreach
+        op.  Nothing is left on the modules: the step is handed down the forward and lives on in the autograd nodes."""
         convs = [m for m in self.modules() if isinstance(m, nn.Conv3d) and m.weight.shape[0] % 16 == 0
                  and m.weight.dtype == torch.float32 and m.weight.shape[2] in (1, 3)]
-        plan = getattr(self, "_pack_plan", None)
-        if plan is None or plan[0] != str(device):
+        sizes = [c.weight.shape[2] ** 3 * c.weight.shape[0] * ((c.weight.shape[1] + 15) // 16 * 16) for c in convs]
+        plan = self._pack_plan
+        if plan is None or plan.device != str(device):
             total = sum(c.weight.numel() for c in convs)
             chunks, spans, off, pos = [], [], 0, 0
             for c in convs:
@@ -946,37 +938,31 @@ class UNet3d(nn.Module):  # pylint: disable=too-many-instance-attributes
                 spans.append((pos, pos + fidx.numel(), pos + fidx.numel() + bidx.numel()))
                 pos += fidx.numel() + bidx.numel()
                 off += n
-            plan = (str(device), torch.cat(chunks), spans)
-            self._pack_plan = plan
+            plan = self._pack_plan = _PackPlan(str(device), torch.cat(chunks), spans)
         theta = torch.cat([c.weight.detach().reshape(-1) for c in convs] + [torch.zeros(1, device=device)])
-        packs = theta[plan[1]]
+        packs = theta[plan.index]
         # one zero-filled buffer for all weight gradients of this step (the kernels accumulate with atomics)
         need_dw = torch.is_grad_enabled() and any(c.weight.requires_grad for c in convs)
-        sizes = [c.weight.shape[2] ** 3 * c.weight.shape[0] * ((c.weight.shape[1] + 15) // 16 * 16) for c in convs]
-        det = _det()             # ONE reading per step: sizes dwall and goes to every node that gets a slice of it
+        det = _det()             # ONE reading per step: sizes dwall and goes to every node the step serves
         dwall = _acc_zeros(sum(sizes), device, det) if need_dw else None
         aw = _acc_w(det)
         defer = None
         if need_dw and self.deferred_weight_grads:
-            defer = _DeferredGrads(convs, dwall, sizes, device, det)
-            if len(plan) < 4:
-                plan = plan + (_DeferredGrads.unpack_index(convs, sizes, device),)
-                self._pack_plan = plan
-            defer.uidx = plan[3]
-        o = 0
-        for i, (c, (a, b, e), n) in enumerate(zip(convs, plan[2], sizes)):
-            co, ci, k = c.weight.shape[0], c.weight.shape[1], c.weight.shape[2]
+            if plan.uidx is None:
+                plan.uidx = _DeferredGrads.unpack_index(convs, sizes, device)
+            defer = _DeferredGrads(convs, dwall, plan.uidx, device, det)
+        steps, o = {}, 0
+        for i, (c, (a, b, e), n) in enumerate(zip(convs, plan.spans, sizes)):
             dw = dwall[aw * o:aw * (o + n)] if need_dw else None      # (flat: the kernels index [tap][co][ci padded] themselves)
-            c._stpde_packs = (packs[a:b], packs[b:e], dw, det) + ((defer, i) if defer is not None else ())
+            steps[c] = _ConvStep(packs[a:b], packs[b:e], dw, det, defer, i)
             o += n
-        bns = []
+        scratch, counted = {}, False
         if self.training:
-            bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm3d) and m.track_running_stats
+            bns = [m.num_batches_tracked for m in self.modules() if isinstance(m, nn.BatchNorm3d) and m.track_running_stats
                    and m.num_batches_tracked is not None]
             if bns:
-                torch._foreach_add_([m.num_batches_tracked for m in bns], 1)
-                for m in bns:
-                    m._stpde_counted = True
+                torch._foreach_add_(bns, 1)
+            counted = True
             # one zero-filled buffer for the statistics scratch of every BatchNorm of the step (forward + backward sums):
             # one memset instead of two per BatchNorm call
             allbn = [m for m in self.modules() if isinstance(m, nn.BatchNorm3d)]
@@ -984,42 +970,30 @@ class UNet3d(nn.Module):  # pylint: disable=too-many-instance-attributes
             zero = torch.zeros(per * sum(m.num_features for m in allbn), device=device)
             o = 0
             for m in allbn:
-                m._stpde_scratch = zero[o:o + per * m.num_features]
+                scratch[m] = zero[o:o + per * m.num_features]
                 o += per * m.num_features
-        return convs, bns
+        return _UNetStep(det, steps, scratch, counted, defer)
 
     def forward(self, x):
         """x [batch, in_features, *igres] -> [batch, out_features, *ogres] (channels-last strides; reference :208-240)."""
-        if not x.is_cuda:
-            return self._forward_impl(x)
-        convs, bns = self._prepare_step(x.device)
-        try:
-            return self._forward_impl(x)
-        finally:
-            for c in convs:
-                c._stpde_packs = None
-            for m in bns:
-                m._stpde_counted = False
-            for m in self.modules():
-                if isinstance(m, nn.BatchNorm3d):
-                    m._stpde_scratch = None
+        return self._forward_impl(x, self._prepare_step(x.device) if x.is_cuda else None)
 
-    def _forward_impl(self, x):
-        h = self.conv_in.forward_cl(x.permute(0, 2, 3, 4, 1).contiguous())
+    def _forward_impl(self, x, step=None):
+        h = self.conv_in.forward_cl(x.permute(0, 2, 3, 4, 1).contiguous(), step)
         skips = [h]
         for mod, kernel in zip(self.down_modules, self._pool_kernels):
-            h = _pool_cl(mod.forward_cl(skips[-1]), kernel)
+            h = _pool_cl(mod.forward_cl(skips[-1], step), kernel)
             skips.append(h)
         h = skips.pop(-1)
-        h = self.conv_mid.forward_cl(_upsample_cl(h, self._up_factors[0]))
+        h = self.conv_mid.forward_cl(_upsample_cl(h, self._up_factors[0]), step)
         for mod, factors in zip(self.up_modules, self._up_factors[1:]):
             h = torch.cat([h, skips.pop(-1)], dim=-1)
-            h = _upsample_cl(mod.forward_cl(h), factors)
+            h = _upsample_cl(mod.forward_cl(h, step), factors)
         h = torch.cat([h, skips.pop(-1)], dim=-1)
         if self.expand:
             for mod, factors in zip(self.exp_modules, self._exp_factors):
-                h = _upsample_cl(mod.forward_cl(h), factors)
-        h = self.conv_out.forward_cl(h)
+                h = _upsample_cl(mod.forward_cl(h, step), factors)
+        h = self.conv_out.forward_cl(h, step)
         if h.is_cuda and h.requires_grad:
             h = _ContiguousGrad.apply(h)
         return h.permute(0, 4, 1, 2, 3)

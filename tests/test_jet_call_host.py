@@ -139,3 +139,45 @@ def test_unet_accumulators_are_sized_by_the_mode_they_are_given(monkeypatch, fla
     x = torch.zeros(1, 2, 2, 2, 16)
     assert unet3d._desc(x, 16, 16, 1, 0, 0).det == 0 and unet3d._desc(x, 16, 16, 1, 0, 1).det == 1
     assert unet3d._desc(x, 16, 16, 1).det == int(flag)        # (no mode given: the caller's own forward-time reading)
+
+
+@pytest.mark.parametrize("flag", [False, True])
+def test_unet_step_record_carries_the_step_and_leaves_the_modules_alone(monkeypatch, flag):
+    """UNet3d._prepare_step returns the per-forward record (unet3d._UNetStep): one reading of the mode, the _ConvStep of every
+    convolution (same packs as the stand-alone constructor, disjoint slices that tile the step's gradient buffer), each
+    BatchNorm's scratch handed out once -- and no ``_stpde*`` attribute on any module, after it or after a forward."""
+    monkeypatch.setattr(_lib, "deterministic", flag)
+    torch.manual_seed(0)
+    net = unet3d.UNet3d(in_features=4, out_features=32, igres=(4, 16, 16), nf=16, mf=64).train()
+    cpu, det = torch.device("cpu"), int(flag)
+    step = net._prepare_step(cpu)
+    monkeypatch.setattr(_lib, "deterministic", not flag)          # (what the step read is what it keeps)
+    convs = [m for m in net.modules() if isinstance(m, torch.nn.Conv3d)]
+    assert step.det == det and len(convs) == 40 and set(step.convs) == set(convs)
+    spans = []
+    for conv in convs:
+        cs, alone = step.convs[conv], unet3d._ConvStep.alone(conv.weight, cpu, det)
+        assert torch.equal(cs.fpack, alone.fpack) and torch.equal(cs.bpack, alone.bpack)
+        assert cs.det == det and cs.defer is None and (alone.dw, alone.defer) == (None, None)
+        co, ci, k = conv.weight.shape[:3]
+        assert cs.dw.numel() == unet3d._acc_w(det) * k ** 3 * co * ((ci + 15) // 16 * 16)
+        assert cs.dw.is_contiguous() and not cs.dw.any()
+        spans.append((cs.dw.storage_offset(), cs.dw.storage_offset() + cs.dw.numel()))
+    spans.sort()
+    total = step.convs[convs[0]].dw.untyped_storage().nbytes() // 4
+    assert spans[0][0] == 0 and spans[-1][1] == total == unet3d._acc_w(det) * 451072
+    assert all(a[1] == b[0] for a, b in zip(spans, spans[1:]))    # pairwise disjoint, and together the whole buffer
+    assert len({cs.dw.untyped_storage().data_ptr() for cs in step.convs.values()}) == 1
+    bns = [m for m in net.modules() if isinstance(m, torch.nn.BatchNorm3d)]
+    assert step.counted and all(int(bn.num_batches_tracked) == 1 for bn in bns)
+    for bn in bns:
+        sc = step.take_scratch(bn)
+        assert sc.numel() == 6 * _lib.BN_REP * bn.num_features and not sc.any()
+        assert step.take_scratch(bn) is None                      # once per BatchNorm and step: then "bring your own"
+
+    def stray():
+        return [(name, a) for name, m in net.named_modules() for a in vars(m) if a.startswith("_stpde")]
+
+    assert stray() == []
+    net(torch.randn(2, 4, 4, 16, 16))
+    assert stray() == []

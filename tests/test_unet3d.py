@@ -524,6 +524,56 @@ def test_deterministic_mode_of_a_unet_step_is_the_one_its_forward_saw(hiplib, mo
         assert torch.equal(a, b), (k, (a - b).abs().max().item())
 
 
+_two_forward_runs = {}
+
+
+def _two_forwards_one_backward(fused, deferred):
+    """(input gradients, parameter gradients, buffers, counter advance) of y1 = net(x1); y2 = net(x2); one backward of both, in
+    deterministic mode; computed once per setting (STPDE_FUSED_RESBLOCK is the caller's to set)"""
+    if (fused, deferred) in _two_forward_runs:
+        return _two_forward_runs[(fused, deferred)]
+    dev = torch.device("cuda:0")
+    torch.manual_seed(31)
+    net = unet3d.UNet3d(in_features=4, out_features=32, igres=(4, 16, 16), nf=16, mf=64).to(dev).train()
+    net.deferred_weight_grads = deferred
+    g = torch.Generator().manual_seed(32)
+    x1, x2 = (torch.randn(2, 4, 4, 16, 16, generator=g).to(dev).requires_grad_(True) for _ in range(2))
+    c1, c2 = (torch.randn(2, 32, 4, 16, 16, generator=g).to(dev) for _ in range(2))
+    before = {n: int(b) for n, b in net.named_buffers() if n.endswith("num_batches_tracked")}
+    nfused = unet3d.stats["fused_resblocks"]
+    y1 = net(x1)
+    y2 = net(x2)
+    assert (unet3d.stats["fused_resblocks"] > nfused) == fused
+    (y1 * c1).sum().add((y2 * c2).sum()).backward()
+    torch.cuda.synchronize()
+    assert all(p.grad is not None for p in net.parameters())
+    out = ([x1.grad.clone(), x2.grad.clone()], [p.grad.clone() for p in net.parameters()],
+           [b.clone() for b in net.buffers()],
+           {int(b) - before[n] for n, b in net.named_buffers() if n.endswith("num_batches_tracked")})
+    _two_forward_runs[(fused, deferred)] = out
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("deferred", [True, False])
+def test_two_forwards_before_one_backward_keep_their_steps_apart(hiplib, monkeypatch, deferred, fused):
+    """Two forwards of the same network, then ONE backward through both: each forward's per-step state (packs, gradient
+    slices, BatchNorm scratch, deferred-gradient object) lives in its own step record and its autograd nodes, so the second
+    forward takes nothing from the first.  In deterministic mode the deferred and the in-line weight gradients of that
+    backward agree bit for bit -- both input gradients, every parameter gradient, every buffer -- on the fused and on the
+    layer-wise path, and every BatchNorm counted two batches.  Batch 2: the deepest BatchNorm sees its minimum of 2 voxels."""
+    from space_time_pde_amd import _lib
+    monkeypatch.setattr(_lib, "deterministic", True)
+    monkeypatch.setenv("STPDE_FUSED_RESBLOCK", "1" if fused else "0")
+    got, ref = _two_forwards_one_backward(fused, deferred), _two_forwards_one_backward(fused, not deferred)
+    assert got[3] == {2} and ref[3] == {2}
+    for k in range(3):
+        assert len(got[k]) == len(ref[k])
+        for i, (a, b) in enumerate(zip(got[k], ref[k])):
+            assert torch.equal(a, b), (k, i, (a.double() - b.double()).abs().max().item())
+
+
 @pytest.mark.gpu
 def test_long_accumulator_finalize_matches_fp64(hiplib):
     """csrc/common.h det_add_f32 / det_value through the public pair (stpde_conv3d_wgrad with det = 1, stpde_det_finalize): a

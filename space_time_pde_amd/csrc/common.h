@@ -253,8 +253,9 @@ __device__ __forceinline__ ActD act_eval_t(float prm, float a) {
     r.s3 = big ? 0.f : q * (1.f - 2.f * s);
   } else if (ACT == STPDE_ACT_ELU) {
     const bool pos = a > 0.f;
-    const float e = fast_exp(fminf(a, 0.f));
-    r.s0 = pos ? a : expm1f(fminf(a, 0.f));
+    const float am = pos ? 0.f : a;  // min(a, 0) that keeps a NaN: fminf(NaN, 0) is 0, i.e. value 0 and slope 1 for a NaN input
+    const float e = fast_exp(am);
+    r.s0 = pos ? a : expm1f(am);
     r.s1 = pos ? 1.f : e;
     r.s2 = pos ? 0.f : e;
     r.s3 = pos ? 0.f : e;

@@ -1,185 +1,225 @@
-// Local-implicit-grid glue kernels for dim = 3:
-//   k_gather      clip + cell index + corner gather + relative coords  -> augmented MLP input X (fragment layout)
-//                 and per-point interpolation coefficients               (src/regular_nd_grid_interpolation.py:48-76,
-//                                                                         src/local_implicit_grid.py:49)
-//   k_reduce_fwd  corner-weighted sum of the MLP output on every derivative stream (src/local_implicit_grid.py:59
-//                 and what the src/pde.py:8-9 sweeps differentiate through)
-//   k_reduce_bwd  its adjoint
-//   k_xbar        d latent: xbar = sum_l W_s,l^T abar_l, scatter-added at the 8 corner nodes (backward of the
-//                 advanced-index gather at src/regular_nd_grid_interpolation.py:65-66)
-//   k_gather_nd / k_reduce_nd   the gather and corner sum for dim = 1, 2, 4 (end of this file)
-//   k_reduce_nd_bwd / k_cell_nd / k_dlat_reduce_nd   what the training backward on such grids adds to the dim-agnostic layer,
-//                 weight-gradient and k_xbar kernels: adjoint of the corner sum, cell id per point, per-node d-latent sum
+// Local-implicit-grid glue kernels around the IM-NET layer kernels, for grids of dim = 1, 2, 3, 4.  One set of templated
+// device bodies serves every dimension; dim = 3 (the PDE path, with derivative streams) adds a per-point epilogue:
+//   gather_row<D> / row_feature<D>   clip + cell index + corner gather + relative coordinates -> augmented MLP input X
+//                 (fragment layout)   (src/regular_nd_grid_interpolation.py:48-76, src/local_implicit_grid.py:49)
+//                 k_gather_nd<D>      D = 1, 2, 4: X and the corner weight of every row (roww)
+//                 k_gather            D = 3: X, the optional row-major image XR, and write_coef()
+//                 k_gather_tile       D = 3, 32 latent channels: the same rows through an LDS patch, 16-byte loads / stores
+//   write_coef    dim = 3 epilogue: per-point interpolation coefficients, cell id, combined-stream weights
+//   point_cell<D> the cell of a point: what the gathers read, what k_cell_nd<D> and write_coef() report
+//   dlat_reduce<D>  per-node d-latent sum in a fixed order: k_dlat_reduce (D = 3), k_dlat_reduce_nd<D> (D = 1, 2, 4)
+//   k_reduce_fwd / k_reduce_bwd       dim = 3: corner-weighted sum of the MLP output on every derivative stream
+//                 (src/local_implicit_grid.py:59 and what the src/pde.py:8-9 sweeps differentiate through) and its adjoint
+//   k_reduce_nd / k_reduce_nd_bwd     D = 1, 2, 4: the value-only corner sum and its adjoint
+//   k_xbar        d latent: xbar = sum_l W_s,l^T abar_l, scatter-added at the corner nodes or written per row (backward of the
+//                 advanced-index gather at src/regular_nd_grid_interpolation.py:65-66); dimension-agnostic
+// The geometry itself (clip, cell index, weights, relative coordinates, their jets) is written in interp_geom.h only.
 // All of these are HBM/L2-bound byte movers; no MFMA except the small xbar GEMM.
 #include "interp_geom.h"
 
-struct PointGeom {
-  float om[2][3];   // omega[b][d] = |q_d - pos_opposite| / cube_d
-  float dom[2][3];  // d omega / d q_d (sign * s_d / cube_d)
-  float rel[2][3];  // (q_d - pos) / cube_d
-  float kap[3];     // s_d / cube_d
-  int i0[3];
-};
-
-// Same fp32 expression sequence as the reference (division, no reciprocal, no contraction).
-__device__ __forceinline__ PointGeom point_geom(const float* p, const float* lo_c, const float* hi_c,
-                                                const float* cube, const int* n) {
-  PointGeom gm;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const float x = p[d];
-    const float m = fminf(x, hi_c[d]);
-    const float q = fmaxf(m, lo_c[d]);
-    // derivative of the clip: min/max backward split ties evenly (quirk a-Q2)
-    const float s = (x < hi_c[d] ? 1.f : (x == hi_c[d] ? 0.5f : 0.f)) * (m > lo_c[d] ? 1.f : (m == lo_c[d] ? 0.5f : 0.f));
-    const float cs = cube[d];
-    const float fl = floorf(q / cs);
-    int i0 = (int)fl;
-    i0 = i0 < 0 ? 0 : (i0 > n[d] - 2 ? n[d] - 2 : i0);  // only NaN / out-of-box inputs ever hit the clamp
-    const float i0f = (float)i0;
-    const float p0 = i0f * cs;
-    const float p1 = (i0f + 1.f) * cs;
-    gm.i0[d] = i0;
-    gm.kap[d] = s / cs;
-    // bit 0: pos = p0, opposite = p1 ; bit 1: pos = p1, opposite = p0
-    const float t0 = q - p1, t1 = q - p0;
-    gm.om[0][d] = fabsf(t0) / cs;
-    gm.om[1][d] = fabsf(t1) / cs;
-    gm.dom[0][d] = (t0 > 0.f ? 1.f : (t0 < 0.f ? -1.f : 0.f)) / cs * s;
-    gm.dom[1][d] = (t1 > 0.f ? 1.f : (t1 < 0.f ? -1.f : 0.f)) / cs * s;
-    gm.rel[0][d] = (q - p0) / cs;
-    gm.rel[1][d] = (q - p1) / cs;
+// ---------------------------------------------------------------------------------------------------------
+// argument checks shared by the entry points
+// ---------------------------------------------------------------------------------------------------------
+// every axis holds a cell and a node index (batch included) fits an int32; *nodes = B * prod(n).  int32_nodes = false leaves the
+// second condition out (stpde_lig_dlatent_reduce never had it, and which calls an entry point refuses is part of the ABI)
+static int check_grid(const char* who, int D, int B, const int* n, size_t* nodes, bool int32_nodes = true) {
+  unsigned long long cnt = (unsigned long long)B;
+  for (int k = 0; k < D; ++k) {
+    if (n[k] < 2) {
+      stpde_set_error("%s: grid axis %d has %d nodes (>= 2 per axis)", who, k, n[k]);
+      return STPDE_E_BADARG;
+    }
+    cnt *= (unsigned long long)n[k];
+    if (int32_nodes && cnt >= (1ull << 31)) {
+      stpde_set_error("%s: latent grid too large for an int32 node index", who);
+      return STPDE_E_BADARG;
+    }
   }
-  return gm;
+  *nodes = (size_t)cnt;
+  return STPDE_OK;
 }
 
+// the features [r(D); latent(C); 1] fit the augmented input: two full tiles and register 0 of the sparse third one
+static int check_features(const char* who, int D, int C) {
+  if (C < 1 || D + C + 1 > 16 * (XT - 1) + 4) {
+    stpde_set_error("%s: D + C + 1 = %d features do not fit the augmented input (<= %d)", who, D + C + 1, 16 * (XT - 1) + 4);
+    return STPDE_E_BADARG;
+  }
+  return STPDE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// gather
+// ---------------------------------------------------------------------------------------------------------
+// A row tile holds 16 >> D points; row j of a tile = corner (j & (2^D - 1)) of point tile * (16 >> D) + (j >> D), corners in
+// the order of interp_nd.hip (first axis most significant).  Feature f of the augmented input [r(D); latent(C); 1] sits in
+// slot f of tiles 0 / 1 and in register 0 of the sparse third tile (x_live()).
+//
+// Addresses, for D = 1, 2, 3, 4 alike.  Every index below is bounded for EVERY input value, not only for points inside the box
+// (tests/lig_nd_model.py restates the bodies; tests/test_lig_nd_host.py runs them on NaN, infinite and huge coordinates):
+//   pts     p < P (rows of p >= P are padding: zeros, weight 0, no read; dim = 3 has none: P is even, ntiles = P / 2), k < D
+//   latent  batch clamped to B - 1, cell index clamped to [0, n_k - 2] by geom_axis() after the float clip (NaN and huge
+//           coordinates end there), corner bit 0 / 1, channel f - D < C: node < B * prod(n), all in 64-bit
+//   X, XR   gid < ntiles * XT * 64 (the grid is derived from ntiles alone), one float4 per thread
+//   roww    tile * 16 + j < ntiles * 16
+//   coef, cell, cw   p < P: one lane per point (corner 0 of the first input tile)
 struct GatherArgs {
-  stpde_gather_desc d;
+  stpde_gather_nd_desc d;   // dim = 3: the fields of stpde_gather_desc, ntiles = P / 2
   const float* pts;
   const float* latent;
   float* X;
-  float* XR;
+  float* roww;              // D = 1, 2, 4: corner weight of every row
+  float* XR;                // dim = 3 from here on
   float* coef;
   int* cell;
   float* cw;
+  float alpha[6];
 };
 
-// Clipped coordinate and cell index of one dimension (the part of point_geom every lane needs): the same fp32 expression
-// sequence, so the index is bit-identical.
-__device__ __forceinline__ int cell_index_1d(float x, float lo, float hi, float cs, int n, float& q) {
-  q = fmaxf(fminf(x, hi), lo);
-  int i0 = (int)floorf(q / cs);
-  return i0 < 0 ? 0 : (i0 > n - 2 ? n - 2 : i0);        // only NaN / out-of-box inputs ever hit the clamp
+// Geometry of point p of the chunk and its cell = the linear index of the cell's corner-0 node, batch included.  The one place
+// that says which cell a point lies in: the gathers read the corners of this cell, k_cell_nd and write_coef() report it.
+template <int D>
+__device__ __forceinline__ size_t point_cell(const stpde_gather_nd_desc& d, const float* pts, size_t p, GeomJet& gj) {
+#pragma unroll
+  for (int k = 0; k < D; ++k) geom_axis_jet(gj, k, pts[p * D + k], d.lo_c[k], d.hi_c[k], d.cube[k], d.n[k]);
+  unsigned b = ((unsigned)d.p_base + (unsigned)p) / (unsigned)d.N;   // (fits: two non-negative ints)
+  b = b > (unsigned)(d.B - 1) ? (unsigned)(d.B - 1) : b;
+  size_t node = b;
+#pragma unroll
+  for (int k = 0; k < D; ++k) node = node * (size_t)d.n[k] + (size_t)gj.i0[k];
+  return node;
 }
 
-// one thread per (tile, xt, lane): writes one float4 of X.
-// Round 3: a lane evaluates only what ITS slot needs -- the three IEEE divisions of the cell index always, the relative
-// coordinates only in the 16 lanes that hold them (tile 0, lane group 0), the full geometry (weights, weight derivatives,
-// clip derivative: 21 more divisions) only in the one lane per point that writes the coefficients (the first version ran
-// point_geom in all 192 lanes of a row tile).  Same results bit for bit; the launch time did not move (1.45 ms per 2^20
-// points either way): the kernel is bound by its 6 KiB of X / XR stores per point, not by the divisions.
-__global__ __launch_bounds__(256) void k_gather(GatherArgs a) {
+struct GatherRow {
+  size_t p, cell, node;   // point of the chunk, its cell, the grid node of this row's corner
+  int corner;
+  float w;                // corner weight
+  GeomJet gj;
+};
+
+// row j of row tile `tile`; false for a padding row (p >= P), of which nothing else is set
+template <int D>
+__device__ __forceinline__ bool gather_row(const GatherArgs& a, size_t tile, int j, GatherRow& r) {
+  constexpr int TP = 16 >> D, NC = 1 << D;
+  r.p = tile * TP + (j >> D);
+  r.corner = j & (NC - 1);
+  if (r.p >= (size_t)a.d.P) return false;
+  r.cell = point_cell<D>(a.d, a.pts, r.p, r.gj);
+  size_t off = 0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) off = off * (size_t)a.d.n[k] + (size_t)corner_bit(r.corner, D, k);
+  r.node = r.cell + off;
+  r.w = corner_weight(r.gj, r.corner, D);
+  return true;
+}
+
+// relative coordinate of the row's corner along axis k = feature k of the augmented input row
+template <int D>
+__device__ __forceinline__ float row_rel(const GatherRow& r, int k) {
+  float val = 0.f;
+#pragma unroll
+  for (int d = 0; d < D; ++d)
+    if (k == d) val = corner_bit(r.corner, D, d) ? r.gj.rl[1][d] : r.gj.rl[0][d];
+  return val;
+}
+
+// feature f >= D of the augmented input row: latent channels of the corner node, the bias column, zeros
+template <int D>
+__device__ __forceinline__ float row_feature(const GatherArgs& a, const GatherRow& r, int f) {
+  const int C = a.d.C;
+  if (f < D + C) return a.latent[r.node * (size_t)C + (size_t)(f - D)];
+  return f == D + C ? 1.f : 0.f;  // bias column
+}
+
+// dim = 3, one lane per point: coef[p][16] = {om[b][d] (6), dom[b][d] (6), kap[d] (3), 0}, cell[p], and the weights of the
+// combined second-order stream cw[p][8] = alpha_k * kappa_a * kappa_b over the canonical pairs
+__device__ __forceinline__ void write_coef(const GatherArgs& a, const GatherRow& r) {
+  const GeomJet& gj = r.gj;
+  float* cf = a.coef + r.p * 16;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    cf[d] = gj.om[0][d];
+    cf[3 + d] = gj.om[1][d];
+    cf[6 + d] = gj.dom[0][d];
+    cf[9 + d] = gj.dom[1][d];
+    cf[12 + d] = gj.kap[d];
+  }
+  cf[15] = 0.f;
+  a.cell[r.p] = (int)r.cell;
+  if (a.cw) {
+    float* cwp = a.cw + r.p * 8;
+    const float k0 = gj.kap[0], k1 = gj.kap[1], k2 = gj.kap[2];
+    cwp[0] = a.alpha[0] * k0 * k0;
+    cwp[1] = a.alpha[1] * k0 * k1;
+    cwp[2] = a.alpha[2] * k0 * k2;
+    cwp[3] = a.alpha[3] * k1 * k1;
+    cwp[4] = a.alpha[4] * k1 * k2;
+    cwp[5] = a.alpha[5] * k2 * k2;
+    cwp[6] = 0.f;
+    cwp[7] = 0.f;
+  }
+}
+
+// one thread per (tile, xt, lane): writes one float4 of X.  A lane evaluates only what ITS slot needs: the divisions of the cell
+// index always, the relative coordinates only in the 16 lanes that hold them (tile 0, lane group 0: features 0 .. D - 1 <= 3),
+// the weights and their jets only where roww / the coefficients are written (each use sits in one branch, and the compiler
+// sinks the unused rest of geom_axis_jet() into it).  The kernel is bound by its stores, not by the divisions.
+template <int D>
+__device__ __forceinline__ void gather_rows(const GatherArgs& a) {
   const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const int ntiles = a.d.P / 2;
-  if (gid >= (size_t)ntiles * XT * 64) return;
+  if (gid >= (size_t)a.d.ntiles * XT * 64) return;
   const int lane = gid & 63;
   const int xt = (gid >> 6) % XT;
-  const int tile = (gid >> 6) / XT;
+  const size_t tile = (gid >> 6) / XT;
   const int g = lane >> 4, j = lane & 15;
-  const int p = tile * 2 + (j >> 3);
-  const int corner = j & 7;
-  const int bit[3] = {(corner >> 2) & 1, (corner >> 1) & 1, corner & 1};
-  const int n[3] = {a.d.n0, a.d.n1, a.d.n2};
-  float pt[3] = {a.pts[(size_t)p * 3], a.pts[(size_t)p * 3 + 1], a.pts[(size_t)p * 3 + 2]};
-  float q[3];
-  int i0[3];
+  const bool head = xt == 0 && g == 0;
+  GatherRow row;
+  f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+  float w = 0.f;
+  if (gather_row<D>(a, tile, j, row)) {
+    if (head) {
 #pragma unroll
-  for (int d = 0; d < 3; ++d) i0[d] = cell_index_1d(pt[d], a.d.lo_c[d], a.d.hi_c[d], a.d.cube[d], n[d], q[d]);
-  int b = (a.d.p_base + p) / a.d.N;
-  b = b > a.d.B - 1 ? a.d.B - 1 : b;
-  const size_t node0 = (((size_t)b * n[0] + i0[0]) * n[1] + i0[1]) * n[2] + i0[2];
-  const size_t node = node0 + ((size_t)bit[0] * n[1] + bit[1]) * n[2] + bit[2];
-  const int C = a.d.C;
-  f32x4 v;
+      for (int r = 0; r < 4; ++r) v[r] = r < D ? row_rel<D>(row, r) : row_feature<D>(a, row, r);
+      if (D != 3)
+        w = row.w;
+      else if (row.corner == 0)
+        write_coef(a, row);
+    } else {
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    // feature held by slot (xt, g, r): tiles 0 / 1 in order, tile 2 sparse (register 0 only: features 32 + g)
-    const int f = xt < XT - 1 ? 16 * xt + 4 * g + r : (r == 0 ? 16 * xt + g : 16 * XT);
-    float val = 0.f;
-    if (f < 3) {
-      // relative coordinate of this corner along dimension f: (q - pos) / cube, pos = (i0 + bit) * cube (reference :69-76)
-      const float cs = sel3(f, a.d.cube[0], a.d.cube[1], a.d.cube[2]);
-      const float qq = sel3(f, q[0], q[1], q[2]);
-      const int ii = f == 0 ? i0[0] : (f == 1 ? i0[1] : i0[2]);
-      const int bb = f == 0 ? bit[0] : (f == 1 ? bit[1] : bit[2]);
-      const float i0f = (float)ii;
-      const float pos = bb ? (i0f + 1.f) * cs : i0f * cs;
-      val = (qq - pos) / cs;
-    } else if (f < 3 + C)
-      val = a.latent[node * C + (f - 3)];
-    else if (f == 3 + C)
-      val = 1.f;  // bias column
-    v[r] = val;
+      for (int r = 0; r < 4; ++r)  // slot (xt, g, r): tiles 0 / 1 in feature order, tile 2 sparse (register 0 only: features 32 + g)
+        v[r] = row_feature<D>(a, row, xt < XT - 1 ? 16 * xt + 4 * g + r : (r == 0 ? 16 * xt + g : 16 * XT));
+    }
   }
   st4(a.X + gid * 4, v);
-  if (a.XR) st_R(a.XR + (gid >> 6) * 256, lane, v);
-  if (xt == 0 && g == 0 && corner == 0) {
-    const PointGeom gm = point_geom(pt, a.d.lo_c, a.d.hi_c, a.d.cube, n);
-    float* cf = a.coef + (size_t)p * 16;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      cf[d] = gm.om[0][d];
-      cf[3 + d] = gm.om[1][d];
-      cf[6 + d] = gm.dom[0][d];
-      cf[9 + d] = gm.dom[1][d];
-      cf[12 + d] = gm.kap[d];
-    }
-    cf[15] = 0.f;
-    a.cell[p] = (int)node0;
-    if (a.cw) {  // weights of the combined second-order stream: alpha_k * kappa_a * kappa_b over the canonical pairs
-      float* cwp = a.cw + (size_t)p * 8;
-      const float k0 = gm.kap[0], k1 = gm.kap[1], k2 = gm.kap[2];
-      cwp[0] = a.d.alpha[0] * k0 * k0;
-      cwp[1] = a.d.alpha[1] * k0 * k1;
-      cwp[2] = a.d.alpha[2] * k0 * k2;
-      cwp[3] = a.d.alpha[3] * k1 * k1;
-      cwp[4] = a.d.alpha[4] * k1 * k2;
-      cwp[5] = a.d.alpha[5] * k2 * k2;
-      cwp[6] = 0.f;
-      cwp[7] = 0.f;
-    }
-  }
+  if (D == 3) {
+    if (a.XR) st_R(a.XR + (gid >> 6) * 256, lane, v);
+  } else if (head)
+    a.roww[tile * 16 + j] = w;
 }
 
-// The same kernel for the reference's 32 latent channels, one WAVE per row tile (round 3): a lane (g, j) fetches channels
-// 8g .. 8g+7 of the grid node of corner row j as two aligned 16-byte loads (the first version: four dword loads per lane,
-// unaligned by the three coordinate features in front of the channels), the 16 x 36 feature rows of the tile go through an
-// LDS patch, and BOTH fragment images of the three input tiles leave as coalesced 16-byte stores (the row-major image used
-// to be four strided dword stores per lane).  Same expressions for the cell index / relative coordinates, bit for bit.
+template <int D>
+__global__ __launch_bounds__(256) void k_gather_nd(GatherArgs a) {
+  gather_rows<D>(a);
+}
+
+__global__ __launch_bounds__(256) void k_gather(GatherArgs a) { gather_rows<3>(a); }
+
+// dim = 3 with the reference's 32 latent channels, one WAVE per row tile (round 3): a lane (g, j) fetches channels
+// 8g .. 8g+7 of the grid node of corner row j as two aligned 16-byte loads (k_gather: four dword loads per lane, unaligned by
+// the three coordinate features in front of the channels), the 16 x 36 feature rows of the tile go through an LDS patch, and
+// BOTH fragment images of the three input tiles leave as coalesced 16-byte stores (k_gather's row-major image is four strided
+// dword stores per lane).  The rows and the epilogue are the shared ones.
 __global__ __launch_bounds__(256) void k_gather_tile(GatherArgs a) {
   constexpr int RS = 36;                       // floats per row: features 0..35 = rel(3), 32 channels, the ones column
   __shared__ __attribute__((aligned(16))) float rows[4][16 * RS];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int ntiles = a.d.P / 2;
   const int tile = blockIdx.x * 4 + wv;
-  const bool live = tile < ntiles;
+  const bool live = tile < a.d.ntiles;
   const int g = lane >> 4, j = lane & 15;
   float* rw = rows[wv];
-  if (live) {
-    const int p = tile * 2 + (j >> 3);
-    const int corner = j & 7;
-    const int bit[3] = {(corner >> 2) & 1, (corner >> 1) & 1, corner & 1};
-    const int n[3] = {a.d.n0, a.d.n1, a.d.n2};
-    float pt[3] = {a.pts[(size_t)p * 3], a.pts[(size_t)p * 3 + 1], a.pts[(size_t)p * 3 + 2]};
-    float q[3];
-    int i0[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) i0[d] = cell_index_1d(pt[d], a.d.lo_c[d], a.d.hi_c[d], a.d.cube[d], n[d], q[d]);
-    int b = (a.d.p_base + p) / a.d.N;
-    b = b > a.d.B - 1 ? a.d.B - 1 : b;
-    const size_t node0 = (((size_t)b * n[0] + i0[0]) * n[1] + i0[1]) * n[2] + i0[2];
-    const size_t node = node0 + ((size_t)bit[0] * n[1] + bit[1]) * n[2] + bit[2];
-    const f32x4 c0 = ld4(a.latent + node * 32 + 8 * g), c1 = ld4(a.latent + node * 32 + 8 * g + 4);
+  GatherRow row;
+  if (live && gather_row<3>(a, tile, j, row)) {
+    const f32x4 c0 = ld4(a.latent + row.node * 32 + 8 * g), c1 = ld4(a.latent + row.node * 32 + 8 * g + 4);
     float* rj = rw + j * RS;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -188,40 +228,9 @@ __global__ __launch_bounds__(256) void k_gather_tile(GatherArgs a) {
     }
     if (g == 0) {
 #pragma unroll
-      for (int f = 0; f < 3; ++f) {
-        // relative coordinate of this corner along dimension f: (q - pos) / cube, pos = (i0 + bit) * cube (reference :69-76)
-        const float cs = a.d.cube[f];
-        const float i0f = (float)i0[f];
-        const float pos = bit[f] ? (i0f + 1.f) * cs : i0f * cs;
-        rj[f] = (q[f] - pos) / cs;
-      }
+      for (int f = 0; f < 3; ++f) rj[f] = row_rel<3>(row, f);
       rj[35] = 1.f;                            // bias column
-      if (corner == 0) {
-        const PointGeom gm = point_geom(pt, a.d.lo_c, a.d.hi_c, a.d.cube, n);
-        float* cf = a.coef + (size_t)p * 16;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-          cf[d] = gm.om[0][d];
-          cf[3 + d] = gm.om[1][d];
-          cf[6 + d] = gm.dom[0][d];
-          cf[9 + d] = gm.dom[1][d];
-          cf[12 + d] = gm.kap[d];
-        }
-        cf[15] = 0.f;
-        a.cell[p] = (int)node0;
-        if (a.cw) {  // weights of the combined second-order stream: alpha_k * kappa_a * kappa_b over the canonical pairs
-          float* cwp = a.cw + (size_t)p * 8;
-          const float k0 = gm.kap[0], k1 = gm.kap[1], k2 = gm.kap[2];
-          cwp[0] = a.d.alpha[0] * k0 * k0;
-          cwp[1] = a.d.alpha[1] * k0 * k1;
-          cwp[2] = a.d.alpha[2] * k0 * k2;
-          cwp[3] = a.d.alpha[3] * k1 * k1;
-          cwp[4] = a.d.alpha[4] * k1 * k2;
-          cwp[5] = a.d.alpha[5] * k2 * k2;
-          cwp[6] = 0.f;
-          cwp[7] = 0.f;
-        }
-      }
+      if (row.corner == 0) write_coef(a, row);
     }
   }
   __syncthreads();
@@ -245,23 +254,107 @@ __global__ __launch_bounds__(256) void k_gather_tile(GatherArgs a) {
 
 extern "C" int stpde_lig_gather(const stpde_gather_desc* d, const float* pts, const float* latent, float* X,
                                 float* XR, float* coef, int* cell, float* cw, void* stream) {
-  if (!d || d->P <= 0 || (d->P & 1) || d->N <= 0 || d->p_base < 0 || d->B <= 0 || d->n0 < 2 || d->n1 < 2 || d->n2 < 2 || d->C < 1 ||
-      3 + d->C + 1 > 16 * (XT - 1) + 4 || !pts || !latent || !X || !coef || !cell) {
-    stpde_set_error("lig_gather: bad argument (P even, grid >= 2 per dim, C <= %d)", 16 * (XT - 1));
+  if (!d || d->P <= 0 || (d->P & 1) || d->N <= 0 || d->p_base < 0 || d->B <= 0 || !pts || !latent || !X || !coef || !cell) {
+    stpde_set_error("lig_gather: bad argument (P even)");
     return STPDE_E_BADARG;
   }
-  if ((size_t)d->B * d->n0 * d->n1 * d->n2 >= (1u << 31)) {
-    stpde_set_error("lig_gather: latent grid too large for int32 node index");
-    return STPDE_E_BADARG;
-  }
-  GatherArgs a{*d, pts, latent, X, XR, coef, cell, cw};
+  GatherArgs a{};
+  a.d.D = 3, a.d.P = d->P, a.d.N = d->N, a.d.B = d->B, a.d.C = d->C, a.d.p_base = d->p_base, a.d.ntiles = d->P / 2;
+  a.d.n[0] = d->n0, a.d.n[1] = d->n1, a.d.n[2] = d->n2;
+  for (int k = 0; k < 3; ++k) a.d.lo_c[k] = d->lo_c[k], a.d.hi_c[k] = d->hi_c[k], a.d.cube[k] = d->cube[k];
+  for (int k = 0; k < 6; ++k) a.alpha[k] = d->alpha[k];
+  size_t nodes;
+  int rc = check_features("lig_gather", 3, d->C);
+  if (!rc) rc = check_grid("lig_gather", 3, d->B, a.d.n, &nodes);
+  if (rc) return rc;
+  a.pts = pts, a.latent = latent, a.X = X, a.XR = XR, a.coef = coef, a.cell = cell, a.cw = cw;
   if (d->C == 32) {       // the reference's latent width: one wave per row tile, 16-byte loads and stores
-    STPDE_LAUNCH(k_gather_tile, dim3((unsigned)((d->P / 2 + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+    STPDE_LAUNCH(k_gather_tile, dim3((unsigned)((a.d.ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
     return stpde_check_launch("k_gather_tile");
   }
-  const size_t nthreads = (size_t)(d->P / 2) * XT * 64;
+  const size_t nthreads = (size_t)a.d.ntiles * XT * 64;
   STPDE_LAUNCH(k_gather, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   return stpde_check_launch("k_gather");
+}
+
+template <int D>
+static int launch_gather_nd(const GatherArgs& a, hipStream_t stream) {
+  const size_t nthreads = (size_t)a.d.ntiles * XT * 64;
+  STPDE_LAUNCH(k_gather_nd<D>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, stream, a);
+  return stpde_check_launch("k_gather_nd");
+}
+
+// D, P against ntiles, and the 32-bit limits shared by the n-D entry points
+static int check_nd(const char* who, int D, int P, int ntiles) {
+  if (D != 1 && D != 2 && D != 4) {
+    stpde_set_error("%s: D = %d (1, 2 or 4; dim = 3 has stpde_lig_gather / stpde_lig_reduce_fwd)", who, D);
+    return STPDE_E_BADARG;
+  }
+  const long TP = 16 >> D;
+  if (P < 1 || ntiles < 1 || (long)ntiles * TP < (long)P || (long)ntiles > ((long)P + TP - 1) / TP + 3 ||
+      (long)ntiles * 16 >= (1L << 31)) {
+    stpde_set_error("%s: P = %d points do not fit ntiles = %d row tiles of %ld points (ceil(P / %ld) <= ntiles <= that + 3)", who,
+                    P, ntiles, TP, TP);
+    return STPDE_E_BADARG;
+  }
+  return STPDE_OK;
+}
+
+// the descriptor checks shared by stpde_lig_gather_nd and stpde_lig_cell_nd
+static int check_gather_nd_desc(const char* who, const stpde_gather_nd_desc* d) {
+  int rc = check_nd(who, d->D, d->P, d->ntiles);
+  if (rc) return rc;
+  if (d->N < 1 || d->B < 1 || d->p_base < 0 || (long)d->p_base + d->P >= (1L << 31)) {
+    stpde_set_error("%s: bad N / B / p_base (p_base + P must fit 31 bits)", who);
+    return STPDE_E_BADARG;
+  }
+  size_t nodes;
+  rc = check_features(who, d->D, d->C);
+  return rc ? rc : check_grid(who, d->D, d->B, d->n, &nodes);
+}
+
+extern "C" int stpde_lig_gather_nd(const stpde_gather_nd_desc* d, const float* pts, const float* latent, float* X, float* roww,
+                                   void* stream) {
+  if (!d || !pts || !latent || !X || !roww) {
+    stpde_set_error("lig_gather_nd: null pointer");
+    return STPDE_E_BADARG;
+  }
+  int rc = check_gather_nd_desc("lig_gather_nd", d);
+  if (rc) return rc;
+  GatherArgs a{};
+  a.d = *d, a.pts = pts, a.latent = latent, a.X = X, a.roww = roww;
+  if (d->D == 1) return launch_gather_nd<1>(a, (hipStream_t)stream);
+  if (d->D == 2) return launch_gather_nd<2>(a, (hipStream_t)stream);
+  return launch_gather_nd<4>(a, (hipStream_t)stream);
+}
+
+// one thread per point: point_cell() as the gather calls it, so cell[p] names exactly the cell whose corners the gather read
+template <int D>
+__global__ __launch_bounds__(256) void k_cell_nd(GatherArgs a) {
+  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= (size_t)a.d.P) return;
+  GeomJet gj;
+  a.cell[p] = (int)point_cell<D>(a.d, a.pts, p, gj);
+}
+
+template <int D>
+static int launch_cell_nd(const GatherArgs& a, hipStream_t stream) {
+  STPDE_LAUNCH(k_cell_nd<D>, dim3((unsigned)(((size_t)a.d.P + 255) / 256)), dim3(256), 0, stream, a);
+  return stpde_check_launch("k_cell_nd");
+}
+
+extern "C" int stpde_lig_cell_nd(const stpde_gather_nd_desc* d, const float* pts, int* cell, void* stream) {
+  if (!d || !pts || !cell) {
+    stpde_set_error("lig_cell_nd: null pointer");
+    return STPDE_E_BADARG;
+  }
+  int rc = check_gather_nd_desc("lig_cell_nd", d);
+  if (rc) return rc;
+  GatherArgs a{};
+  a.d = *d, a.pts = pts, a.cell = cell;
+  if (d->D == 1) return launch_cell_nd<1>(a, (hipStream_t)stream);
+  if (d->D == 2) return launch_cell_nd<2>(a, (hipStream_t)stream);
+  return launch_cell_nd<4>(a, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -485,6 +578,124 @@ extern "C" int stpde_lig_reduce_bwd(const stpde_jet_cfg* cfg, int S_mlp, int P, 
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// corner sum of value-only queries on 1-, 2- and 4-d grids (src/local_implicit_grid.py:59 for the [b, n1..nd, c] grids the
+// reference states its operator for) over the row weights roww of k_gather_nd, and its adjoint
+// ---------------------------------------------------------------------------------------------------------
+struct ReduceNdArgs {
+  int P, n_out;
+  long ldp;
+  const float* src;  // out_pre [ntiles][1][1][256]: lane (g, j) holds output features 4g..4g+3 of row j
+  const float* roww; // [ntiles][16]
+  float* dst;        // y [n_out][ldp]
+};
+
+// one thread per (point, channel): the 2^D corner terms in corner order, fp32.  A point's rows all lie in its own tile and
+// nothing but its own rows and weights is read, so the result does not depend on how the points were chunked.
+// Addresses: p < P <= ntiles * (16 >> D) (checked on the host), ch < n_out <= 16 -> lane < 64; dst index < n_out * ldp.
+template <int D>
+__global__ __launch_bounds__(256) void k_reduce_nd(ReduceNdArgs a) {
+  constexpr int TP = 16 >> D, NC = 1 << D;
+  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (size_t)a.P * a.n_out) return;
+  const size_t p = gid / a.n_out;
+  const int ch = gid % a.n_out;
+  const size_t tile = p / TP;
+  const int j0 = (int)(p % TP) << D;
+  float y = 0.f;
+#pragma unroll
+  for (int corner = 0; corner < NC; ++corner) {
+    const int j = j0 | corner;
+    const int lane = ((ch >> 2) << 4) | j;
+    y += a.roww[tile * 16 + j] * a.src[tile * 256 + lane * 4 + (ch & 3)];
+  }
+  a.dst[(size_t)ch * a.ldp + p] = y;
+}
+
+template <int D>
+static int launch_reduce_nd(const ReduceNdArgs& a, hipStream_t stream) {
+  const size_t n = (size_t)a.P * a.n_out;
+  STPDE_LAUNCH(k_reduce_nd<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  return stpde_check_launch("k_reduce_nd");
+}
+
+extern "C" int stpde_lig_reduce_nd_fwd(int D, int P, int ntiles, int n_out, const float* out_pre, const float* roww, float* y,
+                                       long ldp, void* stream) {
+  if (!out_pre || !roww || !y) {
+    stpde_set_error("lig_reduce_nd_fwd: null pointer");
+    return STPDE_E_BADARG;
+  }
+  int rc = check_nd("lig_reduce_nd_fwd", D, P, ntiles);
+  if (rc) return rc;
+  if (n_out < 1 || n_out > 16 || ldp < P) {
+    stpde_set_error("lig_reduce_nd_fwd: n_out = %d (1..16) or ldp < P", n_out);
+    return STPDE_E_BADARG;
+  }
+  ReduceNdArgs a{P, n_out, ldp, out_pre, roww, y};
+  if (D == 1) return launch_reduce_nd<1>(a, (hipStream_t)stream);
+  if (D == 2) return launch_reduce_nd<2>(a, (hipStream_t)stream);
+  return launch_reduce_nd<4>(a, (hipStream_t)stream);
+}
+
+// Adjoint of k_reduce_nd (training backward on 1-, 2- and 4-d grids).  Row numbering is the gather's: row tile * 16 + j =
+// point * 2^D + corner.  Addresses, bounded for every input value:
+//   abar_out  gid < ntiles * 64, one float4 per thread: all of [ntiles][64][4] is written (zeros for padding rows and features
+//             >= n_out -- the buffer held the forward's fc5 rows and the layer kernels read all of it)
+//   roww      tile * 16 + j < ntiles * 16, read only where p < P
+//   y_bar     (4g + r) * ldp + p with 4g + r < n_out, p < P <= ldp; nothing is read for p >= P
+struct ReduceNdBwdArgs {
+  int P, ntiles, n_out;
+  long ldp;
+  const float* ybar;  // [n_out][ldp]
+  const float* roww;  // [ntiles][16]
+  float* dst;         // abar_out [ntiles][64][4]
+};
+
+// adjoint of k_reduce_nd: one thread per (row tile, lane), one 16-byte store
+template <int D>
+__global__ __launch_bounds__(256) void k_reduce_nd_bwd(ReduceNdBwdArgs a) {
+  constexpr int TP = 16 >> D;
+  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (size_t)a.ntiles * 64) return;
+  const int lane = gid & 63;
+  const size_t tile = gid >> 6;
+  const int g = lane >> 4, j = lane & 15;
+  const size_t p = tile * TP + (j >> D);
+  f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (p < (size_t)a.P && 4 * g < a.n_out) {
+    const float w = a.roww[tile * 16 + j];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (4 * g + r < a.n_out) v[r] = w * a.ybar[(size_t)(4 * g + r) * a.ldp + p];
+  }
+  st4(a.dst + gid * 4, v);
+}
+
+template <int D>
+static int launch_reduce_nd_bwd(const ReduceNdBwdArgs& a, hipStream_t stream) {
+  const size_t n = (size_t)a.ntiles * 64;
+  STPDE_LAUNCH(k_reduce_nd_bwd<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  return stpde_check_launch("k_reduce_nd_bwd");
+}
+
+extern "C" int stpde_lig_reduce_nd_bwd(int D, int P, int ntiles, int n_out, const float* y_bar, long ldp, const float* roww,
+                                       float* abar_out, void* stream) {
+  if (!y_bar || !roww || !abar_out) {
+    stpde_set_error("lig_reduce_nd_bwd: null pointer");
+    return STPDE_E_BADARG;
+  }
+  int rc = check_nd("lig_reduce_nd_bwd", D, P, ntiles);
+  if (rc) return rc;
+  if (n_out < 1 || n_out > 16 || ldp < P) {
+    stpde_set_error("lig_reduce_nd_bwd: n_out = %d (1..16) or ldp < P", n_out);
+    return STPDE_E_BADARG;
+  }
+  ReduceNdBwdArgs a{P, ntiles, n_out, ldp, y_bar, roww, abar_out};
+  if (D == 1) return launch_reduce_nd_bwd<1>(a, (hipStream_t)stream);
+  if (D == 2) return launch_reduce_nd_bwd<2>(a, (hipStream_t)stream);
+  return launch_reduce_nd_bwd<4>(a, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // xbar = sum_l W_s,l^T abar_l (value stream)  ->  scatter-add into d latent
 // ---------------------------------------------------------------------------------------------------------
 struct XbarArgs {
@@ -656,11 +867,12 @@ extern "C" int stpde_lig_xbar_rows(const stpde_xbar_desc* d, const float* const*
 
 static int launch_xbar(const stpde_xbar_desc* d, const float* const* abar, const float* const* WsL_pack,
                        const int* cell, float* dlatent, float* xrows, void* stream) {
-  if (!d || d->ntiles <= 0 || d->nlayers < 1 || d->nlayers > 8 || d->C < 1 || 3 + d->C + 1 > 16 * (XT - 1) + 4 || !abar ||
-      !WsL_pack) {
+  if (!d || d->ntiles <= 0 || d->nlayers < 1 || d->nlayers > 8 || !abar || !WsL_pack) {
     stpde_set_error("lig_xbar: bad argument");
     return STPDE_E_BADARG;
   }
+  int rc = check_features("lig_xbar", 3, d->C);   // (the widest row: the latent of a dim = 3 grid)
+  if (rc) return rc;
   XbarArgs a{};
   a.d = *d;
   for (int l = 0; l < d->nlayers; ++l) {
@@ -685,369 +897,21 @@ static int launch_xbar(const stpde_xbar_desc* d, const float* const* abar, const
 
 // ---------------------------------------------------------------------------------------------------------
 // Deterministic d latent: per-NODE gather of the per-row adjoints written by k_xbar (xrows), in a fixed order
-// (corner 0..7, then the points of the owning cell in ascending point index), instead of fp32 atomics.
+// (corner 0 .. 2^D - 1, then the points of the owning cell in ascending perm position), instead of fp32 atomics.
 // The backward of the advanced-index gather at src/regular_nd_grid_interpolation.py:65-66 is an
 // index_put_(accumulate=True), which is deterministic on the reference's CPU path; so is this.
 //   perm[q]   point index of the q-th point in (stable) cell order
 //   start[c]  first q of the points whose cell (= linear index of the cell's corner-0 node, incl. batch) is c;
 //             start has n_nodes + 1 entries
 // One group of 16 lanes per node (lane = float4 of channels), 4 nodes per wave.
-// ---------------------------------------------------------------------------------------------------------
-struct DlatArgs {
-  int B, n0, n1, n2, C, CP;
-  const float* xrows;   // [8 * P][CP]   row = 8 * point + corner
-  const int* perm;
-  const int* start;
-  float* dlatent;       // [B][n0][n1][n2][C], accumulated into (+=)
-};
-
-__global__ __launch_bounds__(256) void k_dlat_reduce(DlatArgs a) {
-  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const int c4 = gid & 15;
-  const size_t node = gid >> 4;
-  const size_t nnodes = (size_t)a.B * a.n0 * a.n1 * a.n2;
-  if (node >= nnodes || 4 * c4 >= a.CP) return;
-  const int i2 = node % a.n2, i1 = (node / a.n2) % a.n1, i0 = (node / ((size_t)a.n2 * a.n1)) % a.n0;
-  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-  bool any = false;
-#pragma unroll
-  for (int corner = 0; corner < 8; ++corner) {
-    const int b0 = (corner >> 2) & 1, b1 = (corner >> 1) & 1, b2 = corner & 1;
-    const int c0 = i0 - b0, c1 = i1 - b1, c2 = i2 - b2;     // the cell for which this node is corner `corner`
-    if (c0 < 0 || c1 < 0 || c2 < 0 || c0 > a.n0 - 2 || c1 > a.n1 - 2 || c2 > a.n2 - 2) continue;
-    const size_t cell = node - ((size_t)b0 * a.n1 + b1) * a.n2 - b2;
-    const int q0 = a.start[cell], q1 = a.start[cell + 1];
-    for (int q = q0; q < q1; ++q) {
-      const size_t row = (size_t)a.perm[q] * 8 + corner;
-      acc += ld4(a.xrows + row * a.CP + 4 * c4);
-      any = true;
-    }
-  }
-  if (!any) return;
-  float* dst = a.dlatent + node * a.C + 4 * c4;
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    if (4 * c4 + r < a.C) dst[r] += acc[r];
-}
-
-extern "C" int stpde_lig_dlatent_reduce(int B, int n0, int n1, int n2, int C, const float* xrows, const int* perm,
-                                        const int* start, float* dlatent, void* stream) {
-  if (B < 1 || n0 < 2 || n1 < 2 || n2 < 2 || C < 1 || C > 64 || !xrows || !perm || !start || !dlatent) {
-    stpde_set_error("lig_dlatent_reduce: bad argument (C <= 64)");
-    return STPDE_E_BADARG;
-  }
-  DlatArgs a{B, n0, n1, n2, C, (C + 3) / 4 * 4, xrows, perm, start, dlatent};
-  const size_t n = (size_t)B * n0 * n1 * n2 * 16;
-  STPDE_LAUNCH(k_dlat_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return stpde_check_launch("k_dlat_reduce");
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// value-only queries on 1-, 2- and 4-d grids (src/local_implicit_grid.py:47-59 for the [b, n1..nd, c] grids the reference
-// states its operator for): gather into the SAME augmented-input image the layer kernels read, and the corner sum
-// ---------------------------------------------------------------------------------------------------------
-// A row tile holds 16 >> D points; row j of a tile = corner (j & (2^D - 1)) of point tile * (16 >> D) + (j >> D), corners in
-// the order of interp_nd.hip (first axis most significant).  Feature f of the augmented input [r(D); latent(C); 1] sits in
-// slot f of tiles 0 / 1 and in register 0 of the sparse third tile (x_live()), as for dim = 3.
 //
-// Addresses.  Every index below is bounded for EVERY input value, not only for points inside the box:
-//   pts     p < P (rows of p >= P are padding: zeros, weight 0, no read), k < D
-//   latent  batch clamped to B - 1, cell index clamped to [0, n_k - 2] by geom_axis() after the float clip (NaN and huge
-//           coordinates end there), corner bit 0 / 1, channel f - D < C: node < B * prod(n), all in 64-bit
-//   X       gid < ntiles * XT * 64 (the grid is derived from ntiles alone), one float4 per thread
-//   cw      tile * 16 + j < ntiles * 16
-struct GatherNdArgs {
-  stpde_gather_nd_desc d;
-  const float* pts;
-  const float* latent;
-  float* X;
-  float* cw;
-};
-
-template <int D>
-__global__ __launch_bounds__(256) void k_gather_nd(GatherNdArgs a) {
-  constexpr int TP = 16 >> D, NC = 1 << D;
-  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= (size_t)a.d.ntiles * XT * 64) return;
-  const int lane = gid & 63;
-  const int xt = (gid >> 6) % XT;
-  const size_t tile = (gid >> 6) / XT;
-  const int g = lane >> 4, j = lane & 15;
-  const size_t p = tile * TP + (j >> D);
-  const int corner = j & (NC - 1);
-  f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-  float w = 0.f;
-  if (p < (size_t)a.d.P) {
-    GeomN gm;
-#pragma unroll
-    for (int k = 0; k < D; ++k)
-      geom_axis(gm, k, a.pts[p * D + k], a.d.lo_c[k], a.d.hi_c[k], a.d.cube[k], a.d.n[k]);
-    size_t b = ((size_t)a.d.p_base + p) / (size_t)a.d.N;
-    b = b > (size_t)(a.d.B - 1) ? (size_t)(a.d.B - 1) : b;
-    size_t node = b;
-    w = 1.f;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const int bit = corner_bit(corner, D, k);
-      node = node * (size_t)a.d.n[k] + (size_t)(gm.i0[k] + bit);
-      const float o = bit ? gm.om[1][k] : gm.om[0][k];
-      w = (k == 0) ? o : w * o;
-    }
-    const int C = a.d.C;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      // feature held by slot (xt, g, r): tiles 0 / 1 in order, tile 2 sparse (register 0 only: features 32 + g)
-      const int f = xt < XT - 1 ? 16 * xt + 4 * g + r : (r == 0 ? 16 * xt + g : 16 * XT);
-      float val = 0.f;
-      if (f < D) {
-#pragma unroll
-        for (int k = 0; k < D; ++k)
-          if (f == k) val = corner_bit(corner, D, k) ? gm.rl[1][k] : gm.rl[0][k];
-      } else if (f < D + C)
-        val = a.latent[node * (size_t)C + (size_t)(f - D)];
-      else if (f == D + C)
-        val = 1.f;  // bias column
-      v[r] = val;
-    }
-  }
-  st4(a.X + gid * 4, v);
-  if (xt == 0 && g == 0) a.cw[tile * 16 + j] = w;
-}
-
-template <int D>
-static int launch_gather_nd(const GatherNdArgs& a, hipStream_t stream) {
-  const size_t nthreads = (size_t)a.d.ntiles * XT * 64;
-  STPDE_LAUNCH(k_gather_nd<D>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, stream, a);
-  return stpde_check_launch("k_gather_nd");
-}
-
-// D, P against ntiles, and the 32-bit limits shared by the two entry points
-static int check_nd(const char* who, int D, int P, int ntiles) {
-  if (D != 1 && D != 2 && D != 4) {
-    stpde_set_error("%s: D = %d (1, 2 or 4; dim = 3 has stpde_lig_gather / stpde_lig_reduce_fwd)", who, D);
-    return STPDE_E_BADARG;
-  }
-  const long TP = 16 >> D;
-  if (P < 1 || ntiles < 1 || (long)ntiles * TP < (long)P || (long)ntiles > ((long)P + TP - 1) / TP + 3 ||
-      (long)ntiles * 16 >= (1L << 31)) {
-    stpde_set_error("%s: P = %d points do not fit ntiles = %d row tiles of %ld points (ceil(P / %ld) <= ntiles <= that + 3)", who,
-                    P, ntiles, TP, TP);
-    return STPDE_E_BADARG;
-  }
-  return STPDE_OK;
-}
-
-// the descriptor checks shared by stpde_lig_gather_nd and stpde_lig_cell_nd (which must name exactly the cell the gather read)
-static int check_gather_nd_desc(const char* who, const stpde_gather_nd_desc* d) {
-  int rc = check_nd(who, d->D, d->P, d->ntiles);
-  if (rc) return rc;
-  if (d->N < 1 || d->B < 1 || d->p_base < 0 || (long)d->p_base + d->P >= (1L << 31)) {
-    stpde_set_error("%s: bad N / B / p_base (p_base + P must fit 31 bits)", who);
-    return STPDE_E_BADARG;
-  }
-  if (d->C < 1 || d->D + d->C + 1 > 16 * (XT - 1) + 4) {
-    stpde_set_error("%s: D + C + 1 = %d features do not fit the augmented input (<= %d)", who, d->D + d->C + 1,
-                    16 * (XT - 1) + 4);
-    return STPDE_E_BADARG;
-  }
-  unsigned long long nodes = (unsigned long long)d->B;
-  for (int k = 0; k < d->D; ++k) {
-    if (d->n[k] < 2) {
-      stpde_set_error("%s: grid axis %d has %d nodes (>= 2 per axis)", who, k, d->n[k]);
-      return STPDE_E_BADARG;
-    }
-    nodes *= (unsigned long long)d->n[k];
-    if (nodes >= (1ull << 31)) {
-      stpde_set_error("%s: latent grid too large for an int32 node index", who);
-      return STPDE_E_BADARG;
-    }
-  }
-  return STPDE_OK;
-}
-
-extern "C" int stpde_lig_gather_nd(const stpde_gather_nd_desc* d, const float* pts, const float* latent, float* X, float* cw,
-                                   void* stream) {
-  if (!d || !pts || !latent || !X || !cw) {
-    stpde_set_error("lig_gather_nd: null pointer");
-    return STPDE_E_BADARG;
-  }
-  int rc = check_gather_nd_desc("lig_gather_nd", d);
-  if (rc) return rc;
-  GatherNdArgs a{*d, pts, latent, X, cw};
-  if (d->D == 1) return launch_gather_nd<1>(a, (hipStream_t)stream);
-  if (d->D == 2) return launch_gather_nd<2>(a, (hipStream_t)stream);
-  return launch_gather_nd<4>(a, (hipStream_t)stream);
-}
-
-struct ReduceNdArgs {
-  int P, n_out;
-  long ldp;
-  const float* src;  // out_pre [ntiles][1][1][256]: lane (g, j) holds output features 4g..4g+3 of row j
-  const float* cw;   // [ntiles][16]
-  float* dst;        // y [n_out][ldp]
-};
-
-// one thread per (point, channel): the 2^D corner terms in corner order, fp32.  A point's rows all lie in its own tile and
-// nothing but its own rows and weights is read, so the result does not depend on how the points were chunked.
-// Addresses: p < P <= ntiles * (16 >> D) (checked on the host), ch < n_out <= 16 -> lane < 64; dst index < n_out * ldp.
-template <int D>
-__global__ __launch_bounds__(256) void k_reduce_nd(ReduceNdArgs a) {
-  constexpr int TP = 16 >> D, NC = 1 << D;
-  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= (size_t)a.P * a.n_out) return;
-  const size_t p = gid / a.n_out;
-  const int ch = gid % a.n_out;
-  const size_t tile = p / TP;
-  const int j0 = (int)(p % TP) << D;
-  float y = 0.f;
-#pragma unroll
-  for (int corner = 0; corner < NC; ++corner) {
-    const int j = j0 | corner;
-    const int lane = ((ch >> 2) << 4) | j;
-    y += a.cw[tile * 16 + j] * a.src[tile * 256 + lane * 4 + (ch & 3)];
-  }
-  a.dst[(size_t)ch * a.ldp + p] = y;
-}
-
-template <int D>
-static int launch_reduce_nd(const ReduceNdArgs& a, hipStream_t stream) {
-  const size_t n = (size_t)a.P * a.n_out;
-  STPDE_LAUNCH(k_reduce_nd<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
-  return stpde_check_launch("k_reduce_nd");
-}
-
-extern "C" int stpde_lig_reduce_nd_fwd(int D, int P, int ntiles, int n_out, const float* out_pre, const float* cw, float* y,
-                                       long ldp, void* stream) {
-  if (!out_pre || !cw || !y) {
-    stpde_set_error("lig_reduce_nd_fwd: null pointer");
-    return STPDE_E_BADARG;
-  }
-  int rc = check_nd("lig_reduce_nd_fwd", D, P, ntiles);
-  if (rc) return rc;
-  if (n_out < 1 || n_out > 16 || ldp < P) {
-    stpde_set_error("lig_reduce_nd_fwd: n_out = %d (1..16) or ldp < P", n_out);
-    return STPDE_E_BADARG;
-  }
-  ReduceNdArgs a{P, n_out, ldp, out_pre, cw, y};
-  if (D == 1) return launch_reduce_nd<1>(a, (hipStream_t)stream);
-  if (D == 2) return launch_reduce_nd<2>(a, (hipStream_t)stream);
-  return launch_reduce_nd<4>(a, (hipStream_t)stream);
-}
-
+// Addresses, for D = 1, 2, 3, 4 alike (tests/lig_nd_bwd_model.py restates the body):
+//   start     cell and cell + 1 with cell < n_nodes: start has n_nodes + 1 entries
+//   perm      q in [start[cell], start[cell + 1]) within [0, P) (stpde_lig_cell_sort: start[n_nodes] = P)
+//   xrows     row = perm[q] * 2^D + corner < P * 2^D <= 16 * ntiles: inside the [16 * ntiles][CP] rows k_xbar wrote (the
+//             buffer of a chunk is 16 * ntiles * CP floats, padding rows of the last tiles included)
+//   dlatent   node < n_nodes, channel 4 c4 + r < C
 // ---------------------------------------------------------------------------------------------------------
-// training backward on 1-, 2- and 4-d grids: the three kernels around the dimension-agnostic S = (0, 0) layer / weight-gradient
-// kernels and k_xbar (rows variant).  Row numbering is the gather's: row tile * 16 + j = point * 2^D + corner.
-//
-// Addresses.  Every grid below is derived from ntiles, P or the node count alone, and every index is bounded for EVERY
-// input value (NaN, infinite, out-of-box coordinates included):
-//   k_reduce_nd_bwd   abar_out  gid < ntiles * 64, one float4 per thread: all of [ntiles][64][4] is written (zeros for
-//                               padding rows and features >= n_out -- the buffer held the forward's fc5 rows and the layer
-//                               kernels read all of it)
-//                     cw        tile * 16 + j < ntiles * 16, read only where p < P
-//                     y_bar     (4g + r) * ldp + p with 4g + r < n_out, p < P <= ldp; nothing is read for p >= P
-//   k_cell_nd         pts       p < P, k < D;  cell[p], p < P.  Value: batch clamped to B - 1, cell index clamped to
-//                               [0, n_k - 2] by geom_axis() -> cell < B * prod(n) < 2^31 (checked on the host)
-//   k_dlat_reduce_nd  start     cell and cell + 1 with cell < n_nodes: start has n_nodes + 1 entries
-//                     perm      q in [start[cell], start[cell + 1]) within [0, P) (stpde_lig_cell_sort: start[n_nodes] = P)
-//                     xrows     row = perm[q] * 2^D + corner < P * 2^D <= 16 * ntiles: inside the [16 * ntiles][CP] rows k_xbar
-//                               wrote (the buffer of a chunk is 16 * ntiles * CP floats, padding rows of the last tiles included)
-//                     dlatent   node < n_nodes, channel 4 c4 + r < C
-// ---------------------------------------------------------------------------------------------------------
-struct ReduceNdBwdArgs {
-  int P, ntiles, n_out;
-  long ldp;
-  const float* ybar;  // [n_out][ldp]
-  const float* cw;    // [ntiles][16]
-  float* dst;         // abar_out [ntiles][64][4]
-};
-
-// adjoint of k_reduce_nd: one thread per (row tile, lane), one 16-byte store
-template <int D>
-__global__ __launch_bounds__(256) void k_reduce_nd_bwd(ReduceNdBwdArgs a) {
-  constexpr int TP = 16 >> D;
-  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= (size_t)a.ntiles * 64) return;
-  const int lane = gid & 63;
-  const size_t tile = gid >> 6;
-  const int g = lane >> 4, j = lane & 15;
-  const size_t p = tile * TP + (j >> D);
-  f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (p < (size_t)a.P && 4 * g < a.n_out) {
-    const float w = a.cw[tile * 16 + j];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (4 * g + r < a.n_out) v[r] = w * a.ybar[(size_t)(4 * g + r) * a.ldp + p];
-  }
-  st4(a.dst + gid * 4, v);
-}
-
-template <int D>
-static int launch_reduce_nd_bwd(const ReduceNdBwdArgs& a, hipStream_t stream) {
-  const size_t n = (size_t)a.ntiles * 64;
-  STPDE_LAUNCH(k_reduce_nd_bwd<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
-  return stpde_check_launch("k_reduce_nd_bwd");
-}
-
-extern "C" int stpde_lig_reduce_nd_bwd(int D, int P, int ntiles, int n_out, const float* y_bar, long ldp, const float* cw,
-                                       float* abar_out, void* stream) {
-  if (!y_bar || !cw || !abar_out) {
-    stpde_set_error("lig_reduce_nd_bwd: null pointer");
-    return STPDE_E_BADARG;
-  }
-  int rc = check_nd("lig_reduce_nd_bwd", D, P, ntiles);
-  if (rc) return rc;
-  if (n_out < 1 || n_out > 16 || ldp < P) {
-    stpde_set_error("lig_reduce_nd_bwd: n_out = %d (1..16) or ldp < P", n_out);
-    return STPDE_E_BADARG;
-  }
-  ReduceNdBwdArgs a{P, ntiles, n_out, ldp, y_bar, cw, abar_out};
-  if (D == 1) return launch_reduce_nd_bwd<1>(a, (hipStream_t)stream);
-  if (D == 2) return launch_reduce_nd_bwd<2>(a, (hipStream_t)stream);
-  return launch_reduce_nd_bwd<4>(a, (hipStream_t)stream);
-}
-
-struct CellNdArgs {
-  stpde_gather_nd_desc d;
-  const float* pts;
-  int* cell;
-};
-
-// one thread per point: the same geom_axis() calls and the same batch clamp as k_gather_nd, so cell[p] names exactly the cell
-// whose corners the gather read
-template <int D>
-__global__ __launch_bounds__(256) void k_cell_nd(CellNdArgs a) {
-  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= (size_t)a.d.P) return;
-  GeomN gm;
-#pragma unroll
-  for (int k = 0; k < D; ++k) geom_axis(gm, k, a.pts[p * D + k], a.d.lo_c[k], a.d.hi_c[k], a.d.cube[k], a.d.n[k]);
-  size_t b = ((size_t)a.d.p_base + p) / (size_t)a.d.N;
-  b = b > (size_t)(a.d.B - 1) ? (size_t)(a.d.B - 1) : b;
-  size_t node = b;
-#pragma unroll
-  for (int k = 0; k < D; ++k) node = node * (size_t)a.d.n[k] + (size_t)gm.i0[k];
-  a.cell[p] = (int)node;
-}
-
-template <int D>
-static int launch_cell_nd(const CellNdArgs& a, hipStream_t stream) {
-  STPDE_LAUNCH(k_cell_nd<D>, dim3((unsigned)(((size_t)a.d.P + 255) / 256)), dim3(256), 0, stream, a);
-  return stpde_check_launch("k_cell_nd");
-}
-
-extern "C" int stpde_lig_cell_nd(const stpde_gather_nd_desc* d, const float* pts, int* cell, void* stream) {
-  if (!d || !pts || !cell) {
-    stpde_set_error("lig_cell_nd: null pointer");
-    return STPDE_E_BADARG;
-  }
-  int rc = check_gather_nd_desc("lig_cell_nd", d);
-  if (rc) return rc;
-  CellNdArgs a{*d, pts, cell};
-  if (d->D == 1) return launch_cell_nd<1>(a, (hipStream_t)stream);
-  if (d->D == 2) return launch_cell_nd<2>(a, (hipStream_t)stream);
-  return launch_cell_nd<4>(a, (hipStream_t)stream);
-}
-
 struct DlatNdArgs {
   int n[4];
   int C, CP;
@@ -1058,10 +922,9 @@ struct DlatNdArgs {
   float* dlatent;       // [B][n_0..n_{D-1}][C], accumulated into (+=)
 };
 
-// k_dlat_reduce for 2^D corners: one group of 16 lanes per node (lane = float4 of channels); corners 0 .. 2^D - 1 in the order
-// of interp_nd.hip (first axis most significant), the points of the owning cell in ascending perm position, fp32
+// corners in the order of interp_nd.hip (first axis most significant), fp32
 template <int D>
-__global__ __launch_bounds__(256) void k_dlat_reduce_nd(DlatNdArgs a) {
+__device__ __forceinline__ void dlat_reduce(const DlatNdArgs& a) {
   constexpr int NC = 1 << D;
   const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
   const int c4 = gid & 15;
@@ -1109,10 +972,45 @@ __global__ __launch_bounds__(256) void k_dlat_reduce_nd(DlatNdArgs a) {
 }
 
 template <int D>
+__global__ __launch_bounds__(256) void k_dlat_reduce_nd(DlatNdArgs a) {
+  dlat_reduce<D>(a);
+}
+
+__global__ __launch_bounds__(256) void k_dlat_reduce(DlatNdArgs a) { dlat_reduce<3>(a); }
+
+template <int D>
 static int launch_dlat_reduce_nd(const DlatNdArgs& a, hipStream_t stream) {
   const size_t n = a.nnodes * 16;
   STPDE_LAUNCH(k_dlat_reduce_nd<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
   return stpde_check_launch("k_dlat_reduce_nd");
+}
+
+// the checks and the argument record shared by the two entry points
+static int dlat_args(const char* who, int D, int B, const int* n, int C, const float* xrows, const int* perm, const int* start,
+                     float* dlatent, DlatNdArgs* a, bool int32_nodes = true) {
+  if (B < 1 || C < 1 || C > 64) {
+    stpde_set_error("%s: bad B or C = %d (1..64)", who, C);
+    return STPDE_E_BADARG;
+  }
+  *a = DlatNdArgs{};
+  for (int k = 0; k < D; ++k) a->n[k] = n[k];
+  a->C = C, a->CP = (C + 3) / 4 * 4;
+  a->xrows = xrows, a->perm = perm, a->start = start, a->dlatent = dlatent;
+  return check_grid(who, D, B, n, &a->nnodes, int32_nodes);
+}
+
+extern "C" int stpde_lig_dlatent_reduce(int B, int n0, int n1, int n2, int C, const float* xrows, const int* perm,
+                                        const int* start, float* dlatent, void* stream) {
+  if (!xrows || !perm || !start || !dlatent) {
+    stpde_set_error("lig_dlatent_reduce: null pointer");
+    return STPDE_E_BADARG;
+  }
+  const int n[3] = {n0, n1, n2};
+  DlatNdArgs a;
+  int rc = dlat_args("lig_dlatent_reduce", 3, B, n, C, xrows, perm, start, dlatent, &a, false);
+  if (rc) return rc;
+  STPDE_LAUNCH(k_dlat_reduce, dim3((unsigned)((a.nnodes * 16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return stpde_check_launch("k_dlat_reduce");
 }
 
 extern "C" int stpde_lig_dlatent_reduce_nd(int D, int B, const int* n, int C, const float* xrows, const int* perm,
@@ -1125,31 +1023,9 @@ extern "C" int stpde_lig_dlatent_reduce_nd(int D, int B, const int* n, int C, co
     stpde_set_error("lig_dlatent_reduce_nd: D = %d (1, 2 or 4; dim = 3 has stpde_lig_dlatent_reduce)", D);
     return STPDE_E_BADARG;
   }
-  if (B < 1 || C < 1 || C > 64) {
-    stpde_set_error("lig_dlatent_reduce_nd: bad B or C = %d (1..64)", C);
-    return STPDE_E_BADARG;
-  }
-  DlatNdArgs a{};
-  unsigned long long nodes = (unsigned long long)B;
-  for (int k = 0; k < D; ++k) {
-    if (n[k] < 2) {
-      stpde_set_error("lig_dlatent_reduce_nd: grid axis %d has %d nodes (>= 2 per axis)", k, n[k]);
-      return STPDE_E_BADARG;
-    }
-    nodes *= (unsigned long long)n[k];
-    if (nodes >= (1ull << 31)) {
-      stpde_set_error("lig_dlatent_reduce_nd: latent grid too large for an int32 node index");
-      return STPDE_E_BADARG;
-    }
-    a.n[k] = n[k];
-  }
-  a.C = C;
-  a.CP = (C + 3) / 4 * 4;
-  a.nnodes = (size_t)nodes;
-  a.xrows = xrows;
-  a.perm = perm;
-  a.start = start;
-  a.dlatent = dlatent;
+  DlatNdArgs a;
+  int rc = dlat_args("lig_dlatent_reduce_nd", D, B, n, C, xrows, perm, start, dlatent, &a);
+  if (rc) return rc;
   if (D == 1) return launch_dlat_reduce_nd<1>(a, (hipStream_t)stream);
   if (D == 2) return launch_dlat_reduce_nd<2>(a, (hipStream_t)stream);
   return launch_dlat_reduce_nd<4>(a, (hipStream_t)stream);

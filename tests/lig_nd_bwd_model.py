@@ -1,10 +1,13 @@
-"""Numpy model of the three kernels the training backward on 1-, 2- and 4-d local implicit grids adds (host-logic tests only).
+"""Numpy model of the kernels the training backward adds around k_xbar, for local implicit grids of every dimension (host-logic
+tests only).
 
-``cell_nd``, ``reduce_nd_bwd`` and ``dlatent_reduce_nd`` restate k_cell_nd, k_reduce_nd_bwd and k_dlat_reduce_nd of
-csrc/lig_gather_reduce.hip thread by thread -- the same integer arithmetic for every address, including the threads of the
-last block that the bounds test turns away -- and record every element index they read or write, so a CPU test can show that
-no input forms an address outside a buffer before a kernel ever runs.  ``cell_sort`` states what stpde_lig_cell_sort
-promises (stable order, start = points in cells < c).  The geometry is tests/lig_nd_model.py's ``geom_axis``.
+``cell_nd`` and ``dlatent_reduce_nd`` restate the shared bodies of csrc/lig_gather_reduce.hip for D = 1..4 -- point_cell<D>
+(k_cell_nd<D>, and the cell the gathers of every dimension read and the dim = 3 gathers write) and dlat_reduce<D>
+(k_dlat_reduce_nd<D> for D = 1, 2, 4, k_dlat_reduce for D = 3) -- and ``reduce_nd_bwd`` restates k_reduce_nd_bwd, thread by
+thread: the same integer arithmetic for every address, including the threads of the last block that the bounds test turns
+away.  They record every element index they read or write, so a CPU test can show that no input forms an address outside a
+buffer before a kernel ever runs.  ``cell_sort`` states what stpde_lig_cell_sort promises (stable order, start = points in
+cells < c).  The geometry is tests/lig_nd_model.py's ``geom_axis``.
 """
 import numpy as np
 

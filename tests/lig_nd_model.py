@@ -1,8 +1,10 @@
-"""Numpy model of the value-only HIP path for 1-, 2- and 4-d local implicit grids (host-logic tests only).
+"""Numpy model of the gather side of the HIP path for local implicit grids of every dimension (host-logic tests only).
 
-``gather_nd`` restates k_gather_nd of csrc/lig_gather_reduce.hip thread by thread -- the same integer arithmetic for every
-address, the same fp32 expression sequence for the geometry -- and records every element index it reads or writes, so a
-CPU test can show that no input forms an address outside a buffer before the kernel ever runs.  ``reduce_nd`` restates
+``gather_nd`` restates the shared gather body of csrc/lig_gather_reduce.hip (gather_rows<D>, D = 1..4: k_gather_nd<D> for
+D = 1, 2, 4 and k_gather / k_gather_tile for D = 3) thread by thread -- the same integer arithmetic for every address, the
+same fp32 expression sequence for the geometry -- and records every element index it reads or writes, so a CPU test can show
+that no input forms an address outside a buffer before the kernel ever runs.  ``coef_epilogue`` restates what the dim = 3
+gathers add per point (write_coef: coef, cell, cw), ``gather3`` is the whole of stpde_lig_gather.  ``reduce_nd`` restates
 k_reduce_nd, ``mlp_rows`` the layer kernels' one-stream pass over the operand packs (tests/mfma_emu.py).
 """
 import numpy as np
@@ -11,6 +13,9 @@ from tests import mfma_emu as E
 
 XT = 3
 F32 = np.float32
+# the dim = 3 cases (dim, grid, c, xmax) shared by the host tests and tests/test_gpu_lig_glue.py: c = 8 reaches k_gather,
+# c = 32 k_gather_tile
+D3_GRIDS = [(3, (3, 4, 5), 8, (2.0, 1.0, 0.5)), (3, (4, 3, 3), 32, 1.0)]
 
 
 def corner_bit(j, dim, k):
@@ -30,9 +35,71 @@ def geom_axis(x, lo, hi, cs, n):
     return i0, om, rl
 
 
+def geom_axis_jet(x, lo, hi, cs, n):
+    """csrc/interp_geom.h geom_axis_jet in fp32: geom_axis plus the derivative s of the clip (min / max backward split ties
+    evenly), kap = s / cs and dom = sign(q - opposite) / cs * s."""
+    x, lo, hi, cs = F32(x), F32(lo), F32(hi), F32(cs)
+    i0, om, rl = geom_axis(x, lo, hi, cs, n)
+    m = np.fmin(x, hi)
+    q = np.fmax(m, lo)
+    s = F32(1 if x < hi else (0.5 if x == hi else 0)) * F32(1 if m > lo else (0.5 if m == lo else 0))
+    i0f = F32(i0)
+    t = (q - (i0f + F32(1)) * cs, q - i0f * cs)          # q - opposite position of bit 0 / bit 1
+    dom = tuple(F32(1 if tb > 0 else (-1 if tb < 0 else 0)) / cs * s for tb in t)
+    return i0, om, rl, dom, s / cs
+
+
+def coef_epilogue(pts, n, B, N, p_base, lo_c, hi_c, cube, alpha=None):
+    """What one lane per point of the dim = 3 gathers writes: pts [P, 3] fp32 -> coef [P, 16] = {om[b][d] (6), dom[b][d] (6),
+    kap[d] (3), 0}, cell [P] = node of corner 0 (batch clamped) and, with ``alpha`` (6 weights), cw [P, 8] =
+    alpha_k * kap_a * kap_b over the canonical pairs (0,0) (0,1) (0,2) (1,1) (1,2) (2,2), then two zeros; cw is None without."""
+    P = pts.shape[0]
+    coef = np.full((P, 16), np.nan, dtype=F32)
+    cell = np.full(P, -1, dtype=np.int64)
+    cw = None if alpha is None else np.full((P, 8), np.nan, dtype=F32)
+    for p in range(P):
+        g = [geom_axis_jet(pts[p, d], lo_c[d], hi_c[d], cube[d], n[d]) for d in range(3)]
+        for d in range(3):
+            coef[p, d], coef[p, 3 + d] = g[d][1]
+            coef[p, 6 + d], coef[p, 9 + d] = g[d][3]
+            coef[p, 12 + d] = g[d][4]
+        coef[p, 15] = 0
+        node = min((p_base + p) // N, B - 1)
+        for d in range(3):
+            node = node * n[d] + g[d][0]
+        cell[p] = node
+        if cw is not None:
+            k = [g[d][4] for d in range(3)]
+            for i, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+                cw[p, i] = F32(F32(alpha[i]) * k[a]) * k[b]
+            cw[p, 6:] = 0
+    assert cell.max() < 2 ** 31
+    return coef, cell.astype(np.int32), cw
+
+
+def gather3(pts, latent, N, p_base, lo_c, hi_c, cube, alpha=None):
+    """stpde_lig_gather: pts [P, 3] (P even), latent [B, n0, n1, n2, C] -> X [P / 2, 3, 64, 4], coef, cell, cw (None without
+    ``alpha``) and the index sets of gather_nd; every element of coef, cell and cw is written exactly once (one lane per
+    point, p < P)."""
+    P = pts.shape[0]
+    assert P % 2 == 0
+    X, _, touched = gather_nd(3, pts, latent, N, p_base, lo_c, hi_c, cube, P // 2)
+    coef, cell, cw = coef_epilogue(pts, latent.shape[1:4], latent.shape[0], N, p_base, lo_c, hi_c, cube, alpha)
+    return X, coef, cell, cw, touched
+
+
+def row_major_image(X):
+    """The optional XR output of stpde_lig_gather from X [ntiles, 3, 64, 4]: lane 16 g + c of a tile holds rows 4g .. 4g + 3
+    of slot c, where X's lane 16 g + j holds slots 4g .. 4g + 3 of row j."""
+    nt = X.shape[0]
+    rows = X.reshape(nt, XT, 4, 16, 4).transpose(0, 1, 3, 2, 4).reshape(nt, XT, 16, 16)          # [row j][slot 4g + r]
+    return np.ascontiguousarray(rows.reshape(nt, XT, 4, 4, 16).transpose(0, 1, 2, 4, 3)).reshape(nt, XT, 64, 4)
+
+
 def gather_nd(D, pts, latent, N, p_base, lo_c, hi_c, cube, ntiles):
-    """pts [P, D] fp32, latent [B, n_1..n_D, C] fp32 -> X [ntiles, 3, 64, 4], cw [ntiles * 16] and the index sets
-    {"pts", "latent", "X", "cw"} of flat element indices touched."""
+    """pts [P, D] fp32, latent [B, n_1..n_D, C] fp32 -> X [ntiles, 3, 64, 4], cw [ntiles * 16] (the weight of every row: the
+    roww output of k_gather_nd; the dim = 3 kernels do not store it) and the index sets {"pts", "latent", "X", "cw"} of flat
+    element indices touched."""
     TP, NC = 16 >> D, 1 << D
     P, B, C = pts.shape[0], latent.shape[0], latent.shape[-1]
     n = latent.shape[1:-1]

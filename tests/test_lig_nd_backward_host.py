@@ -39,8 +39,10 @@ def _hostile_points(shape, xmax):
 # ---------------------------------------------------------------------------------------------------------------------
 # host model of the addresses
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dim,shape,cin,xmax", GRIDS)
+@pytest.mark.parametrize("dim,shape,cin,xmax", GRIDS + M.D3_GRIDS)
 def test_host_model_addresses_stay_inside_their_buffers(dim, shape, cin, xmax):
+    """dim = 3 (k_dlat_reduce and the cell stpde_lig_gather writes are the same bodies at D = 3): that entry point takes an
+    even P and ntiles = P / 2, so the chunk lengths are rounded up to even there"""
     B, n_out = 2, 3
     pts1 = _hostile_points(shape, xmax)
     N = pts1.shape[0]
@@ -53,6 +55,7 @@ def test_host_model_addresses_stay_inside_their_buffers(dim, shape, cin, xmax):
     # one chunk; chunks that end inside a tile / inside a batch item (P no multiple of the tile's point count; the last one
     # starts past B * N on purpose: the batch index must clamp); ntiles at ceil + 0 and ceil + 3
     for p0, pc in ((0, B * N), (0, 1), (N - 3, tp + 1), (B * N - 2, 2), (B * N + 5, 3)):
+        pc += pc & 1 if dim == 3 else 0
         pc_pts = np.resize(pts[p0:p0 + pc], (pc, dim)) if p0 < B * N else pts[:pc]
         cell, t = MB.cell_nd(dim, pc_pts, shape, B, N, p0, lo_c, hi_c, cube)
         assert t["pts"] == set(range(pc * dim)) and t["cell"] == set(range(pc))
@@ -63,7 +66,7 @@ def test_host_model_addresses_stay_inside_their_buffers(dim, shape, cin, xmax):
         perm, start = MB.cell_sort(cell, n_nodes)
         assert start.shape == (n_nodes + 1,) and start[-1] == pc and sorted(perm.tolist()) == list(range(pc))
         need = -(-pc // tp)
-        for nt in (need, need + 3):
+        for nt in ((need,) if dim == 3 else (need, need + 3)):
             ldp = pc + 5
             ybar = rng.standard_normal((n_out, ldp)).astype(np.float32)
             ybar[:, pc:] = np.nan                                     # beyond the chunk: must not be read

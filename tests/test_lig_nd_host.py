@@ -194,7 +194,44 @@ def test_host_model_addresses_stay_inside_their_buffers(dim, shape, cin, xmax):
         assert max(tr["out_pre"]) < nt * 256 and max(tr["cw"]) < nt * 16 and y.shape == (3, pc)
 
 
-@pytest.mark.parametrize("dim,shape,cin,xmax", GRIDS)
+@pytest.mark.parametrize("dim,shape,cin,xmax", M.D3_GRIDS)
+def test_host_model_addresses_stay_inside_their_buffers_dim3(dim, shape, cin, xmax):
+    """The same for stpde_lig_gather: k_gather / k_gather_tile are the shared gather body at D = 3 (two points per row tile,
+    P even, ntiles = P / 2) plus the per-point coefficient epilogue."""
+    B = 2
+    pts1 = _hostile_points(shape, xmax)
+    N = pts1.shape[0]
+    pts = np.concatenate([pts1, pts1[::-1]], 0)                      # [B * N, 3]
+    rng = np.random.default_rng(1)
+    latent = rng.standard_normal((B,) + shape + (cin,)).astype(np.float32)
+    lo_c, hi_c, cube = lig_jet.box_constants(shape, 0., xmax)
+    alpha = (0.5, -1.0, 2.0, 0.25, 3.0, -0.75)
+    n_nodes = B * int(np.prod(shape))
+    # the chunk starts of the 1-, 2- and 4-d test, the lengths rounded up to the even P this entry point takes
+    for p0, pc in ((0, B * N), (0, 2), (N - 3, 4), (B * N - 2, 2), (B * N + 5, 4)):
+        pc_pts = np.resize(pts[p0:p0 + pc], (pc, dim)) if p0 < B * N else pts[:pc]
+        nt = pc // 2
+        X, coef, cell, cw, t = M.gather3(pc_pts, latent, N, p0, lo_c, hi_c, cube, alpha)
+        assert t["pts"] == set(range(pc * dim))                      # reads every coordinate of the chunk, nothing else
+        assert min(t["latent"]) >= 0 and max(t["latent"]) < latent.size
+        assert t["X"] == set(range(nt * XT * 256))                   # every element written, none outside
+        # coef, cell and cw start as NaN / -1: finite and non-negative means every element was written
+        assert X.shape == (nt, XT, 64, 4) and coef.shape == (pc, 16) and cell.shape == (pc,) and cw.shape == (pc, 8)
+        assert np.isfinite(X).all() and np.isfinite(coef).all() and np.isfinite(cw).all()
+        assert cell.min() >= 0 and cell.max() < n_nodes
+        idx = np.unravel_index(cell, (B,) + shape)                   # a corner-0 node: every corner of it is a node of the grid
+        assert all((idx[1 + k] <= shape[k] - 2).all() for k in range(dim))
+        assert np.all(coef[:, 15] == 0) and np.all(cw[:, 6:] == 0)
+        rows = X.reshape(nt, XT, 4, 16, 4).transpose(0, 3, 1, 2, 4).reshape(nt * 16, XT * 16)
+        slot = ImNetPlan.get(dim, cin, 3, 16).slot
+        assert np.all(rows[:, slot[dim + cin]] == 1)                 # the ones column
+        assert np.all(rows[:, np.setdiff1d(np.arange(16 * XT), slot)] == 0)
+        w = np.stack([np.prod([coef[:, 3 * M.corner_bit(c, 3, k) + k] for k in range(3)], 0) for c in range(8)], 1)
+        np.testing.assert_allclose(w.sum(1), 1.0, atol=1e-5)         # partition of unity
+        assert M.gather3(pc_pts, latent, N, p0, lo_c, hi_c, cube)[3] is None     # cw not requested
+
+
+@pytest.mark.parametrize("dim,shape,cin,xmax", GRIDS + M.D3_GRIDS)
 def test_host_model_geometry_matches_oracle_bitwise(dim, shape, cin, xmax):
     """cell choice, relative coordinates and corner weights of the model (= the kernel's expression sequence) against the
     oracle's interp_coefficients on the edge points: same fp32 operations, so equal to the last bit except the weight product,
@@ -212,6 +249,66 @@ def test_host_model_geometry_matches_oracle_bitwise(dim, shape, cin, xmax):
     np.testing.assert_array_equal(rows[:, slot[:dim]], rel[0].reshape(-1, dim).numpy())
     np.testing.assert_array_equal(rows[:, slot[dim:dim + cin]], v[0].reshape(-1, cin).numpy())
     np.testing.assert_allclose(cw[:P << dim], w[0].reshape(-1).numpy(), rtol=dim * 1.2e-7, atol=1e-12)
+
+
+def _oracle_weight_jets(shape, pts, xmax, dtype):
+    """w [P, 8], dw / dq [P, 8, 3], d2w / dq_a dq_b [P, 8, 3, 3] and d rel_d / dq_d [P, 3] of the oracle's interp_coefficients
+    in ``dtype`` by torch autograd (every point's outputs depend on that point alone, so gradients of sums are per point)"""
+    q = torch.from_numpy(pts)[None].to(dtype).requires_grad_(True)
+    _, w, rel = O.interp_coefficients(torch.zeros((1,) + shape + (1,), dtype=dtype), q, *_box(3, xmax))
+    P = pts.shape[0]
+    dw, ddw = torch.zeros(P, 8, 3, dtype=dtype), torch.zeros(P, 8, 3, 3, dtype=dtype)
+    for c in range(8):
+        g, = torch.autograd.grad(w[0, :, c].sum(), q, create_graph=True)
+        dw[:, c] = g[0].detach()
+        for a in range(3):
+            ddw[:, c, a] = torch.autograd.grad(g[0, :, a].sum(), q, retain_graph=True)[0][0]
+    drel, = torch.autograd.grad(rel[0, :, 0].sum(), q)
+    return w[0].detach(), dw, ddw, drel[0]
+
+
+BOUND = {"w": 5.6e-8, "dw": 9.2e-8, "ddw": 2.6e-6, "w*kap": 9.4e-8}      # the measurement in the docstring below
+
+
+@pytest.mark.parametrize("dim,shape,cin,xmax", M.D3_GRIDS)
+def test_coefficient_model_matches_oracle(dim, shape, cin, xmax):
+    """coef_epilogue (= what the dim = 3 gathers write per point) on the 24 random edge points, all strictly inside a cell and
+    inside the box.  om is the oracle's per-axis weight |q - opposite| / cube, read off the oracle's relative coordinates
+    (|rel| of the corner with the other bit): bit-equal.  The corner weights and their first and second derivatives, rebuilt
+    from coef as corner_weights() of csrc/lig_gather_reduce.hip rebuilds them, and w * kap (the factor the corner sum puts on
+    the decoder's derivative streams) against torch autograd through the fp64 oracle.
+    Bound: 4 x the fp32 oracle's own distance from the fp64 oracle on these points, relative to the largest magnitude of each
+    quantity.  Measured, grid (3, 4, 5) / (4, 3, 3): w 9.4e-8 / 5.6e-8, dw 1.2e-7 / 9.2e-8, ddw 1.0e-5 / 2.6e-6 (autograd's
+    second derivative of a product of six factors), w * kap 9.4e-8 / 9.5e-8; BOUND holds the smaller of each pair.  The model
+    itself sits at 3.0e-8 (6.0e-8 for w * kap on the second grid).
+    Points on a clip bound (where s = 0.5) are tests/test_next_rows.py's clip-tie lattice."""
+    pts = M.edge_points(shape, xmax)[:24]
+    lo_c, hi_c, cube = lig_jet.box_constants(shape, 0., xmax)
+    coef, cell, cw = M.coef_epilogue(pts, shape, 1, 24, 0, lo_c, hi_c, cube, (0.5, -1.0, 2.0, 0.25, 3.0, -0.75))
+    _, _, rel = O.interp_coefficients(torch.zeros((1,) + shape + (1,)), torch.from_numpy(pts)[None], *_box(3, xmax))
+    rel = rel[0].numpy()                                             # [P, 8, 3]
+    for k in range(3):
+        np.testing.assert_array_equal(coef[:, k], np.abs(rel[:, 7, k]))          # om[0]: distance to the bit-1 position
+        np.testing.assert_array_equal(coef[:, 3 + k], np.abs(rel[:, 0, k]))      # om[1]: distance to the bit-0 position
+    assert np.all(coef[:, 12:15] == 1 / np.asarray(cube, np.float32))            # inside the box: s = 1
+    om = lambda c, k: coef[:, 3 * M.corner_bit(c, 3, k) + k].astype(np.float64)
+    dm = lambda c, k: coef[:, 6 + 3 * M.corner_bit(c, 3, k) + k].astype(np.float64)
+    got_w = np.stack([om(c, 0) * om(c, 1) * om(c, 2) for c in range(8)], 1)
+    got_dw = np.stack([np.stack([np.prod([dm(c, k) if k == a else om(c, k) for k in range(3)], 0) for a in range(3)], 1)
+                       for c in range(8)], 1)
+    got_ddw = np.stack([np.stack([np.stack([np.prod([dm(c, k) if k in (a, b) else om(c, k) for k in range(3)], 0) * (a != b)
+                                            for b in range(3)], 1) for a in range(3)], 1) for c in range(8)], 1)
+    got_wk = got_w[:, :, None] * coef[:, None, 12:15].astype(np.float64)
+    w32, dw32, ddw32, dr32 = _oracle_weight_jets(shape, pts, xmax, torch.float32)
+    w64, dw64, ddw64, dr64 = _oracle_weight_jets(shape, pts, xmax, torch.float64)
+    rows = (("w", got_w, w32, w64), ("dw", got_dw, dw32, dw64), ("ddw", got_ddw, ddw32, ddw64),
+            ("w*kap", got_wk, w32[:, :, None] * dr32[:, None], w64[:, :, None] * dr64[:, None]))
+    for name, got, o32, o64 in rows:
+        scale = o64.abs().max().item()
+        own = (o32.double() - o64).abs().max().item() / scale
+        err = np.abs(got - o64.numpy()).max() / scale
+        print("%s %s: fp32 oracle vs fp64 oracle %.2e, model vs fp64 oracle %.2e" % (shape, name, own, err))
+        assert err <= 4 * BOUND[name], (name, err)
 
 
 @pytest.mark.parametrize("dim,shape,cin,xmax", [GRIDS[0], GRIDS[1], GRIDS[3]])

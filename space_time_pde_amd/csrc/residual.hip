@@ -175,7 +175,7 @@ __device__ __forceinline__ float loss_elem(int kind, float d) {
 __device__ __forceinline__ float loss_grad(int kind, float d) {
   if (kind == STPDE_LOSS_L1) return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
   if (kind == STPDE_LOSS_L2) return 2.f * d;
-  return fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : -1.f);
+  return d >= 1.f ? 1.f : (d <= -1.f ? -1.f : d);      // both comparisons are false for NaN: the gradient stays NaN (torch)
 }
 
 __global__ __launch_bounds__(256) void k_loss_sum(LossArgs a) {

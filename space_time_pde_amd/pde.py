@@ -162,8 +162,10 @@ class _ResidualHip(torch.autograd.Function):
     @_lib.guarded
     def forward(ctx, jets, x2d, prog_t, nins, n_eq):
         L = _lib.lib()
-        jets = jets if jets.stride(2) == 1 and jets.stride(1) >= jets.shape[2] else jets.contiguous()
         P, n_out = jets.shape[2], jets.shape[1]
+        # as it is when its rows are unit-stride and neither rows nor streams overlap (dense, or a slice of padded rows)
+        if not (jets.stride(2) == 1 and jets.stride(1) >= P and jets.stride(0) >= (n_out - 1) * jets.stride(1) + P):
+            jets = jets.contiguous()
         res = torch.empty(n_eq, P, device=jets.device, dtype=torch.float32)
         _lib.check(L.stpde_residual_fwd(_lib.ptr(prog_t), nins, n_eq, n_out, P, _lib.ptr(jets), jets.stride(0),
                                         jets.stride(1), _lib.ptr(x2d), _lib.ptr(res), _lib.stream_ptr()))
@@ -179,9 +181,11 @@ class _ResidualHip(torch.autograd.Function):
         jets, x2d, prog_t = ctx.saved_tensors
         nins, n_eq = ctx.meta
         P, n_out = jets.shape[2], jets.shape[1]
-        jbar = torch.zeros_like(jets)      # preserves the strides of jets (dense or sliced-contiguous)
-        if jbar.stride() != jets.stride():
-            raise RuntimeError("residual backward: unexpected jets layout")
+        # jets may be the slice [:, :, :P] of a buffer whose rows are padded (lig_jet.lig_jets at an odd point count), and the
+        # kernel addresses jets_bar with the strides of jets: one zero-filled block of that extent, viewed the same way
+        # (zeros_like would return dense strides for such a slice)
+        extent = (jets.shape[0] - 1) * jets.stride(0) + (n_out - 1) * jets.stride(1) + P
+        jbar = torch.zeros(extent, device=jets.device, dtype=jets.dtype).as_strided(jets.shape, jets.stride())
         _lib.check(L.stpde_residual_bwd(_lib.ptr(prog_t), nins, n_eq, n_out, P, _lib.ptr(jets), jets.stride(0),
                                         jets.stride(1), _lib.ptr(x2d), _lib.ptr(gres.contiguous()), _lib.ptr(jbar),
                                         _lib.stream_ptr()))

@@ -5,34 +5,7 @@ import sympy
 import torch
 
 from space_time_pde_amd import pde as P, physics
-
-
-def _interp(prog, jets, x):
-    """numpy interpreter of the stpde_res_ins program (the semantics documented in include/stpde_hip.h)."""
-    ops = {v: k for k, v in P._RES_OPS.items()}
-    v, out = [], {}
-    for op, a, b, c in prog.tolist():
-        name = ops[op]
-        if name == "JET":
-            r = jets[a, b]
-        elif name == "X":
-            r = x[:, a]
-        elif name == "CONST":
-            r = np.full(jets.shape[2], c)
-        elif name in ("ADD", "SUB", "MUL", "DIV"):
-            r = {"ADD": np.add, "SUB": np.subtract, "MUL": np.multiply, "DIV": np.divide}[name](v[a], v[b])
-        elif name == "NEG":
-            r = -v[a]
-        elif name == "POWI":
-            r = v[a] ** b
-        elif name == "OUT":
-            r = v[a]
-            out[b] = r
-        else:
-            r = {"SIN": np.sin, "COS": np.cos, "EXP": np.exp, "LOG": np.log, "SQRT": np.sqrt, "TANH": np.tanh,
-                 "ABS": np.abs}[name](v[a])
-        v.append(r)
-    return [out[k] for k in sorted(out)]
+from tests import residual_model
 
 
 def _layer_c5():
@@ -71,7 +44,7 @@ def test_ssa_program_matches_lambdify(which):
     n = 50
     jets = rng.standard_normal((len(stream_of), layer.n_out, n))
     x = rng.random((n, 3))
-    got = _interp(prog, jets, x)
+    got = residual_model.run(prog, jets, x, np.float64)   # the interpreter shared with the device tests
     for k, p in enumerate(progs.values()):
         cols = [torch.from_numpy(x[:, i]) for i in range(3)]
         atoms = [torch.from_numpy(jets[stream_of[a[1]], a[0]]) for a in p.atoms]

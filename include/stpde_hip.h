@@ -403,8 +403,8 @@ int stpde_interp_bwd_grid(const stpde_interp_desc* d, const float* pts, const fl
  * ceil(P / (16 >> D)) by up to 3 (the value-tile mode wants a multiple of 4): rows of points >= P are written as zeros
  * with weight 0 and belong to no output point; nothing is read or written past P points or ntiles tiles.  The cell index
  * is clamped to [0, n_k - 2] after the float clip and the batch index to B - 1, so no coordinate value -- NaN, infinite,
- * outside the box -- forms an address outside the latent grid.  No derivative streams (such requests take the composed
- * formulation, local_implicit_grid.py); the training backward of the value stream is the next block.  Refused with STPDE_E_BADARG: D other than 1, 2, 4; P < 1; ntiles
+ * outside the box -- forms an address outside the latent grid.  No derivative streams in these two calls (dim = 1, 2: the
+ * block after the next; dim = 4 requests take the composed formulation, local_implicit_grid.py); the training backward of the value stream is the next block.  Refused with STPDE_E_BADARG: D other than 1, 2, 4; P < 1; ntiles
  * outside [ceil(P / (16 >> D)), that + 3]; an axis with fewer than 2 nodes; D + C + 1 > 36; B * prod(n) or p_base + P
  * beyond 31 bits; n_out outside 1..16; ldp < P; a null pointer. */
 typedef struct {
@@ -447,6 +447,33 @@ int stpde_lig_reduce_nd_bwd(int D, int P, int ntiles, int n_out, const float* y_
 int stpde_lig_cell_nd(const stpde_gather_nd_desc* d, const float* pts, int* cell /* [P] */, void* stream);
 int stpde_lig_dlatent_reduce_nd(int D, int B, const int* n /* [D] on the host */, int C, const float* xrows, const int* perm,
                                 const int* start, float* dlatent, void* stream);
+
+/* ---- coordinate derivatives on the same grids for dim = 1, 2 (forward only) -------------------------------------------
+ * y and its first and selected second derivatives w.r.t. the query coordinates (what the src/pde.py:8-9 sweeps compute) in
+ * one forward pass: stpde_lig_gather_nd, stpde_lig_coef_nd, the layer kernels / stpde_jet_tail_fwd_p unchanged in a stream
+ * set (3, 0), (3, 2), (3, 4) or (3, 6) over ntiles row tiles of 16 >> D points, stpde_lig_reduce_nd_jet_fwd.  The layer
+ * kernels carry three tangent streams whatever D is: the caller's `tanc` packs must hold zeros for the columns d >= D, which
+ * makes the streams of those axes identically zero.  Not served (the caller keeps the composed formulation): D = 4, the
+ * combined second-order stream (its per-row weights are indexed two points per tile), bf16 operands, and any backward.
+ *   stpde_lig_coef_nd            coef[p][16] of stpde_lig_gather for point p of the chunk, from the same clip and cell index
+ *                                as stpde_lig_gather_nd: {om[0][k], om[1][k], dom[0][k], dom[1][k], kap[k]} at 0 / 3 / 6 / 9 /
+ *                                12 + k for k < D; om = 1, dom = 0, kap = 0 for the axes k >= D; entry 15 = 0.  Checks of
+ *                                stpde_lig_gather_nd, and D other than 1, 2 refused.
+ *   stpde_lig_reduce_nd_jet_fwd  jets[(s * n_out + ch) * ldp + p] = sum over the 2^D corners, in corner order, of the terms of
+ *                                stpde_lig_reduce_fwd (w, dw, the d2w cross terms, kappa factors) on row
+ *                                ((p % (16 >> D)) << D) | corner of tile p / (16 >> D) of out_pre [ntiles][S_mlp][1][256].
+ *                                Stream order of dim = 3: value, d/dq_0, d/dq_1, d/dq_2, then the pairs of cfg.  The streams
+ *                                of the axes >= D are stored as +0.0 whatever the inputs hold (never computed as 0 * f).
+ *                                S_mlp < 1 + S1 + S2: streams the layer buffers do not hold count as zero (piecewise-linear
+ *                                activations).  Refused with STPDE_E_BADARG: D other than 1, 2; a null pointer; P < 1 or
+ *                                P > ntiles * (16 >> D) or ntiles > ceil(P / (16 >> D)) + 3; n_out outside 1..16; ldp < P;
+ *                                S1 other than 0, 3; S2 other than 0, 2, 4, 6 (or != 0 with S1 = 0); cfg.combo set; a pair
+ *                                index outside 0 .. D - 1; S_mlp outside 1 .. 1 + S1 + S2.
+ * Nothing is read or written for p >= P; every index is bounded for every coordinate value (NaN, infinite, huge). */
+int stpde_lig_coef_nd(const stpde_gather_nd_desc* d, const float* pts, float* coef /* [P][16] */, void* stream);
+int stpde_lig_reduce_nd_jet_fwd(const stpde_jet_cfg* cfg, int S_mlp, int D, int P, int ntiles, int n_out,
+                                const float* out_pre /* [ntiles][S_mlp][1][256] */, const float* coef,
+                                float* jets /* [S][n_out][ldp] */, long ldp, void* stream);
 
 /* ---- a10: 3-D convolution of the U-Net encoder (src/unet3d.py:39-56: nn.Conv3d 1x1x1 and 3x3x3/pad 1, stride 1)
  * Activations are channels-last: x [B][T][Z][X][Ci], y [B][T][Z][X][Co], Ci and Co multiples of 16.

@@ -250,6 +250,9 @@ _SIGNATURES = {
     "stpde_lig_reduce_nd_bwd": ([C.c_int, C.c_int, C.c_int, C.c_int, _VP, C.c_long, _VP, _VP, _VP], C.c_int),
     "stpde_lig_cell_nd": ([C.POINTER(GatherNdDesc), _VP, _VP, _VP], C.c_int),
     "stpde_lig_dlatent_reduce_nd": ([C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _VP, _VP, _VP, _VP, _VP], C.c_int),
+    "stpde_lig_coef_nd": ([C.POINTER(GatherNdDesc), _VP, _VP, _VP], C.c_int),
+    "stpde_lig_reduce_nd_jet_fwd": ([C.POINTER(JetCfg), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, C.c_long,
+                                     _VP], C.c_int),
     "stpde_jet_layer_fwd": ([C.POINTER(LayerDesc)] + [_VP] * 12, C.c_int),
     "stpde_jet_layer_bwd": ([C.POINTER(LayerDesc)] + [_VP] * 13, C.c_int),
     "stpde_jet_layer_bwd_to": ([C.POINTER(LayerDesc)] + [_VP] * 8, C.c_int),

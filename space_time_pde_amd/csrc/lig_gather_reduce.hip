@@ -11,6 +11,8 @@
 //   k_reduce_fwd / k_reduce_bwd       dim = 3: corner-weighted sum of the MLP output on every derivative stream
 //                 (src/local_implicit_grid.py:59 and what the src/pde.py:8-9 sweeps differentiate through) and its adjoint
 //   k_reduce_nd / k_reduce_nd_bwd     D = 1, 2, 4: the value-only corner sum and its adjoint
+//   k_coef_nd<D> / k_reduce_nd_jet<D> D = 1, 2, forward only: the dim = 3 coefficient record per point and the corner sum of
+//                 every derivative stream over the 16 >> D points-per-tile rows
 //   k_xbar        d latent: xbar = sum_l W_s,l^T abar_l, scatter-added at the corner nodes or written per row (backward of the
 //                 advanced-index gather at src/regular_nd_grid_interpolation.py:65-66); dimension-agnostic
 // The geometry itself (clip, cell index, weights, relative coordinates, their jets) is written in interp_geom.h only.
@@ -693,6 +695,188 @@ extern "C" int stpde_lig_reduce_nd_bwd(int D, int P, int ntiles, int n_out, cons
   if (D == 1) return launch_reduce_nd_bwd<1>(a, (hipStream_t)stream);
   if (D == 2) return launch_reduce_nd_bwd<2>(a, (hipStream_t)stream);
   return launch_reduce_nd_bwd<4>(a, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// coordinate derivatives on 1- and 2-d grids, forward only: the per-point coefficient record and the corner sum of every
+// derivative stream (what the src/pde.py:8-9 sweeps differentiate through, for the [b, n1..nd, c] grids of
+// src/local_implicit_grid.py:10-61).  Between the two run the layer kernels in their (3, 0) / (3, 2) / (3, 4) / (3, 6) stream
+// sets over the 16 >> D points-per-tile image of k_gather_nd<D>; the tangent streams of the axes a grid does not have are
+// identically zero there because the plan's `tanc` columns d >= D are zero (lig_jet.py, ImNetPlan).
+//
+// Addresses, bounded for EVERY input value -- NaN, infinite and huge coordinates included (tests/lig_nd_jet_model.py restates
+// both bodies and records every index; tests/test_lig_nd_jet_host.py runs them on such coordinates):
+//   k_coef_nd        grid from P alone; p < P; pts p * D + k, k < D; coef p * 16 + i, i < 16.  Nothing but pts is read: the
+//                    cell index point_cell() clamps forms no address here.
+//   k_reduce_nd_jet  grid from P * n_out alone; p < P <= ntiles * (16 >> D) (checked on the host), ch < n_out <= 16.
+//                    coef   p * 16 + i, i < 16
+//                    src    tile = p / TP < ntiles, stream s < S_mlp, lane = (ch >> 2) << 4 | j < 64, register ch & 3:
+//                           (tile * S_mlp + s) * 256 + lane * 4 + (ch & 3) < ntiles * S_mlp * 256.  No index depends on a
+//                           value read from memory: the pair indices come from the descriptor and are checked < D on the host.
+//                    dst    (s * n_out + ch) * ldp + p, s < S, p < P <= ldp
+// Nothing is read or written for p >= P.
+// ---------------------------------------------------------------------------------------------------------
+// one thread per point: point_cell<D>() as the gather calls it, so the record describes exactly the cell whose corners the
+// gather read.  Layout of the dim = 3 record (write_coef); an axis the grid does not have gets om = 1, dom = 0, kap = 0.
+template <int D>
+__global__ __launch_bounds__(256) void k_coef_nd(GatherArgs a) {
+  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= (size_t)a.d.P) return;
+  GeomJet gj;
+  point_cell<D>(a.d, a.pts, p, gj);
+  float cf[16];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const bool has = d < D;
+    cf[d] = has ? gj.om[0][d] : 1.f;
+    cf[3 + d] = has ? gj.om[1][d] : 1.f;
+    cf[6 + d] = has ? gj.dom[0][d] : 0.f;
+    cf[9 + d] = has ? gj.dom[1][d] : 0.f;
+    cf[12 + d] = has ? gj.kap[d] : 0.f;
+  }
+  cf[15] = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) st4(a.coef + p * 16 + 4 * i, f32x4{cf[4 * i], cf[4 * i + 1], cf[4 * i + 2], cf[4 * i + 3]});
+}
+
+template <int D>
+static int launch_coef_nd(const GatherArgs& a, hipStream_t stream) {
+  STPDE_LAUNCH(k_coef_nd<D>, dim3((unsigned)(((size_t)a.d.P + 255) / 256)), dim3(256), 0, stream, a);
+  return stpde_check_launch("k_coef_nd");
+}
+
+static int check_jet_dim(const char* who, int D) {
+  if (D != 1 && D != 2) {
+    stpde_set_error("%s: D = %d (coordinate derivatives: 1 or 2; dim = 3 has stpde_lig_gather / stpde_lig_reduce_fwd)", who, D);
+    return STPDE_E_BADARG;
+  }
+  return STPDE_OK;
+}
+
+extern "C" int stpde_lig_coef_nd(const stpde_gather_nd_desc* d, const float* pts, float* coef, void* stream) {
+  if (!d || !pts || !coef) {
+    stpde_set_error("lig_coef_nd: null pointer");
+    return STPDE_E_BADARG;
+  }
+  int rc = check_jet_dim("lig_coef_nd", d->D);
+  if (!rc) rc = check_gather_nd_desc("lig_coef_nd", d);
+  if (rc) return rc;
+  GatherArgs a{};
+  a.d = *d, a.pts = pts, a.coef = coef;
+  return d->D == 1 ? launch_coef_nd<1>(a, (hipStream_t)stream) : launch_coef_nd<2>(a, (hipStream_t)stream);
+}
+
+struct ReduceNdJetArgs {
+  stpde_jet_cfg cfg;   // the streams of dst
+  int P, n_out;
+  int S_mlp;           // streams present in src (piecewise-linear activations carry no second-order streams)
+  long ldp;
+  const float* src;    // out_pre [ntiles][S_mlp][1][256]
+  const float* coef;   // [P][16]
+  float* dst;          // jets [S][n_out][ldp]
+};
+
+// one thread per (point, channel): the 2^D corner terms in corner order with the arithmetic of k_reduce_fwd -- the corner of
+// the dim = 3 record is the corner of the cell with bit 0 on the axes the grid does not have, whose om = 1 leaves every
+// product as it is.  The streams of those axes are not computed at all (0 * f would turn a NaN of the decoder into a NaN of a
+// derivative that is identically zero): they are stored as +0.0.
+template <int D>
+__global__ __launch_bounds__(256) void k_reduce_nd_jet(ReduceNdJetArgs a) {
+  constexpr int TP = 16 >> D, NC = 1 << D;
+  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (size_t)a.P * a.n_out) return;
+  const size_t p = gid / a.n_out;
+  const int ch = gid % a.n_out;
+  const int S1 = a.cfg.S1, S2 = a.cfg.S2, S = 1 + S1 + S2;
+  float cf[16];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f32x4 v = ld4(a.coef + p * 16 + 4 * i);
+    cf[4 * i] = v[0];
+    cf[4 * i + 1] = v[1];
+    cf[4 * i + 2] = v[2];
+    cf[4 * i + 3] = v[3];
+  }
+  const float* kap = cf + 12;
+  float y[10];
+#pragma unroll
+  for (int s = 0; s < 10; ++s) y[s] = 0.f;
+  const size_t tile = p / TP;
+  const int j0 = (int)(p % TP) << D;
+#pragma unroll
+  for (int corner = 0; corner < NC; ++corner) {
+    const int j = j0 | corner;
+    const int lane = ((ch >> 2) << 4) | j;
+    const float* base = a.src + tile * (size_t)a.S_mlp * 256 + lane * 4 + (ch & 3);
+    float f[10];
+#pragma unroll
+    for (int s = 0; s < 10; ++s) f[s] = s < a.S_mlp ? base[(size_t)s * 256] : 0.f;
+    int c3 = 0;   // the corner in the dim = 3 numbering: first axis most significant, absent axes bit 0
+#pragma unroll
+    for (int k = 0; k < D; ++k) c3 |= corner_bit(corner, D, k) << (2 - k);
+    const CornerW c = corner_weights(cf, c3);
+    y[0] += c.w * f[0];
+    if (S1 == 3) {
+#pragma unroll
+      for (int d = 0; d < D; ++d) y[1 + d] += c.dw[d] * f[0] + c.w * kap[d] * f[1 + d];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        if (k < S2) {
+          const int d = a.cfg.pair0[k], e = a.cfg.pair1[k];   // < D (checked on the host)
+          const float kd = sel3(d, kap[0], kap[1], kap[2]), ke = sel3(e, kap[0], kap[1], kap[2]);
+          const float dwd = sel3(d, c.dw[0], c.dw[1], c.dw[2]), dwe = sel3(e, c.dw[0], c.dw[1], c.dw[2]);
+          const float fd = sel3(d, f[1], f[2], f[3]), fe = sel3(e, f[1], f[2], f[3]);
+          y[4 + k] += pair_ddw(c, d, e) * f[0] + dwd * ke * fe + dwe * kd * fd + c.w * kd * ke * f[4 + k];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < 10; ++s)
+    if (s < S) a.dst[((size_t)s * a.n_out + ch) * a.ldp + p] = (s >= 1 + D && s < 4) ? 0.f : y[s];
+}
+
+template <int D>
+static int launch_reduce_nd_jet(const ReduceNdJetArgs& a, hipStream_t stream) {
+  const size_t n = (size_t)a.P * a.n_out;
+  STPDE_LAUNCH(k_reduce_nd_jet<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  return stpde_check_launch("k_reduce_nd_jet");
+}
+
+extern "C" int stpde_lig_reduce_nd_jet_fwd(const stpde_jet_cfg* cfg, int S_mlp, int D, int P, int ntiles, int n_out,
+                                           const float* out_pre, const float* coef, float* jets, long ldp, void* stream) {
+  const char* who = "lig_reduce_nd_jet_fwd";
+  if (!cfg || !out_pre || !coef || !jets) {
+    stpde_set_error("%s: null pointer", who);
+    return STPDE_E_BADARG;
+  }
+  int rc = check_jet_dim(who, D);
+  if (!rc) rc = check_nd(who, D, P, ntiles);
+  if (rc) return rc;
+  if (n_out < 1 || n_out > 16 || ldp < P) {
+    stpde_set_error("%s: n_out = %d (1..16) or ldp < P", who, n_out);
+    return STPDE_E_BADARG;
+  }
+  if ((cfg->S1 != 0 && cfg->S1 != 3) || (cfg->S2 != 0 && cfg->S2 != 2 && cfg->S2 != 4 && cfg->S2 != 6) ||
+      (cfg->S1 == 0 && cfg->S2 != 0)) {
+    stpde_set_error("%s: stream set (S1, S2) = (%d, %d): S1 0 or 3, S2 0, 2, 4 or 6 (with S1 = 3)", who, cfg->S1, cfg->S2);
+    return STPDE_E_BADARG;
+  }
+  if (cfg->combo) {
+    stpde_set_error("%s: the combined second-order stream is dim = 3 only", who);
+    return STPDE_E_BADARG;
+  }
+  for (int k = 0; k < cfg->S2; ++k)
+    if (cfg->pair0[k] < 0 || cfg->pair0[k] >= D || cfg->pair1[k] < 0 || cfg->pair1[k] >= D) {
+      stpde_set_error("%s: pair %d = (%d, %d) names an axis a D = %d grid does not have", who, k, cfg->pair0[k], cfg->pair1[k], D);
+      return STPDE_E_BADARG;
+    }
+  if (S_mlp < 1 || S_mlp > 1 + cfg->S1 + cfg->S2) {
+    stpde_set_error("%s: S_mlp = %d outside 1..%d", who, S_mlp, 1 + cfg->S1 + cfg->S2);
+    return STPDE_E_BADARG;
+  }
+  ReduceNdJetArgs a{*cfg, P, n_out, S_mlp, ldp, out_pre, coef, jets};
+  return D == 1 ? launch_reduce_nd_jet<1>(a, (hipStream_t)stream) : launch_reduce_nd_jet<2>(a, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -36,3 +36,32 @@ def evaluate_feat_grid(pde_layer, latent_grid, t_seq, z_seq, x_seq, mins=None, m
             res[name].append(val.detach().cpu().numpy()[..., 0])
     shape = [nb, len(t_seq), len(z_seq), len(x_seq)]
     return {k: np.concatenate(v, axis=1).reshape(shape)[0] for k, v in res.items()}
+
+
+def evaluate_lattice(pde_layer, latent_grid, seqs, channels, pseudo_batch_size=1 << 20):
+    """``evaluate_feat_grid`` for a problem of any dimension: evaluate the (already updated) pde_layer forward method on the
+    lattice seqs[0] x ... x seqs[d - 1], one 1-D tensor per input variable of the layer, in its ``in_vars`` order.
+
+    Returns {name in ``channels`` (the outputs, in order) or equation name: ndarray [len(seqs[0]), ..., len(seqs[d - 1])]} for
+    batch element 0.  Grad mode as in ``evaluate_feat_grid``: off where the layer answers with forward-mode jets (for 1- and
+    2-d problems that is the opt-in ``lig_jet.nd_jets``; whether it does is asked with grad mode off, the mode those jets
+    need), on for the reverse sweeps of the generic strategy.
+    """
+    device = latent_grid.device
+    nb, d = latent_grid.shape[0], len(seqs)
+    coord = torch.stack(torch.meshgrid(*seqs, indexing="ij"), dim=-1).reshape(-1, d).to(device)
+    n_query = coord.shape[0]
+    res = defaultdict(list)
+    for sid in range(0, n_query, pseudo_batch_size):
+        batch = coord[sid:sid + pseudo_batch_size][None].expand(nb, -1, d).contiguous()
+        with torch.no_grad():
+            jet = getattr(pde_layer, "_jet_request", lambda x: None)(batch) is not None
+        with (torch.no_grad() if jet else torch.enable_grad()):
+            pred, residues = pde_layer(batch, return_residue=True)
+            pred = pred.detach().cpu().numpy()
+        for cid, name in enumerate(channels):
+            res[name].append(pred[..., cid])
+        for name, val in residues.items():
+            res[name].append(val.detach().cpu().numpy()[..., 0])
+    shape = [nb] + [len(s) for s in seqs]
+    return {k: np.concatenate(v, axis=1).reshape(shape)[0] for k, v in res.items()}

@@ -1,5 +1,5 @@
 """Host driver of the fused LIG + IM-NET jet path (dim = 3; value queries, and opt-in their training backward, also for
-dim = 1, 2, 4) on libstpde_hip.
+dim = 1, 2, 4; opt-in forward-only jets also for dim = 1, 2) on libstpde_hip.
 
 Computes y = query_local_implicit_grid(imnet, latent, pts) together with its first and selected second
 derivatives w.r.t. the query coordinates ("jets") in one forward pass of HIP kernels, and the gradients w.r.t.
@@ -45,6 +45,20 @@ def set_nd_backward(on):
     prev, nd_backward = nd_backward, bool(on)
     return prev
 
+
+# Opt-in: coordinate derivatives (first and second-order pairs) of queries on 1- and 2-d grids in HIP, for forward passes that
+# need no gradient (``set_nd_jets`` / STPDE_ND_JETS=1, read once here).  Off, lig_jets refuses a derivative request on such a
+# grid and PDELayer runs its reverse sweeps through the composed formulation, as before.
+ND_JET_DIMS = (1, 2)
+nd_jets = os.getenv("STPDE_ND_JETS", "0").strip().lower() not in ("", "0", "false", "no", "off")
+
+
+def set_nd_jets(on):
+    """Switch the HIP coordinate derivatives of dim = 1, 2 queries on or off; returns the previous setting."""
+    global nd_jets
+    prev, nd_jets = nd_jets, bool(on)
+    return prev
+
 # Optional per-kernel timing (bench.py): set ``profile`` to a dict; every library call then records a pair of
 # events on the launch stream under its kernel name.  None = no overhead.
 profile = None
@@ -87,8 +101,8 @@ class ImNetPlan:
         # dim = 3: the jet path.  dim = 1, 2, 4: the packs serve the value path (lig_jets with first=False, pairs=()) and its
         # training backward -- the layer kernels index the augmented input by SLOT ("Ws", the latent columns "WsL" of the
         # d-latent GEMM and the unpack map of the weight gradients all go through the slot map), and in their one-stream
-        # configuration nothing reads the "tanc" packs (columns 0..2 as coordinate tangents), which mean something for
-        # dim = 3 only
+        # configuration nothing reads the "tanc" packs (columns 0..2 as coordinate tangents).  dim = 1, 2 (``nd_jets``): the
+        # derivative streams run on the same kernels, "tanc" holds zeros for the columns that are no coordinate
         if dim != 3 and dim not in ND_VALUE_DIMS:
             raise ValueError("the HIP path is built for dim=3 query points (value-only queries: dim 1, 2, 4)")
         if nf % 16 != 0:
@@ -176,9 +190,15 @@ class ImNetPlan:
             wsl = aug[(16 * mt[:, None, None, None] + 4 * g[None, None, :, None] + r[None, None, None, :]),
                       (16 * KT + slot[self.dim + np.minimum(ch, self.cin - 1)])]
             add("WsL", np.where(ch < self.cin, wsl, zero))
+            # tangent constants W_s[:, d] of the three coordinate streams.  dim = 1, 2: column d >= dim of the augmented input
+            # is a latent channel, not a coordinate -- the stream of an axis the grid does not have starts from zeros and stays
+            # identically zero (dim = 4 keeps the columns as they were: nothing carries derivative streams there)
             d = np.arange(3)
-            add("tanc", aug[(16 * mt[None, :, None, None] + 4 * g[None, None, :, None] + r[None, None, None, :]),
-                            (16 * KT + d)[:, None, None, None] + 0 * mt[None, :, None, None]])
+            tanc = aug[(16 * mt[None, :, None, None] + 4 * g[None, None, :, None] + r[None, None, None, :]),
+                       (16 * KT + d)[:, None, None, None] + 0 * mt[None, :, None, None]]
+            if self.dim in ND_JET_DIMS:
+                tanc[self.dim:] = zero
+            add("tanc", tanc)
             self.pack_off.append(offs)
             self.dw_off.append((dwo, Mp, Ka))
             dwo += Mp * Ka
@@ -402,6 +422,7 @@ class JetCall:
     fused_tail: bool        # fc3 -> fc5 in one kernel where ``tail`` / a value-tile pass allows
     fc1_fused: bool         # bf16 mode: fused backward of the first hidden layer (STPDE_FC1_FUSED)
     nd_backward: bool       # dim = 1, 2, 4: the HIP training backward is allowed
+    nd_jets: bool           # dim = 1, 2: coordinate derivatives in HIP are allowed (forward passes that need no gradient)
     pipeline: bool          # driver: one library call per direction (dim = 3, no per-kernel profile), else kernel by kernel
     # ---- derived, computed once
     tail: bool              # the fused fc3 -> fc5 kernels serve this call's training stream set (_tail_applies)
@@ -450,7 +471,8 @@ class JetCall:
                    chunk=max(mult, chunk_points // mult * mult), need_grad=bool(need_grad), det=bool(_lib.deterministic),
                    det_dlatent=bool(deterministic_dlatent), value_tiles=bool(value_tiles), tan0_rowsum=bool(tan0_rowsum),
                    wgrad_split=bool(wgrad_split), fused_tail=bool(fused_tail), fc1_fused=fc1_fused_enabled(),
-                   nd_backward=bool(nd_backward), pipeline=bool(use_pipeline and profile is None and dim == 3),
+                   nd_backward=bool(nd_backward), nd_jets=bool(nd_jets),
+                   pipeline=bool(use_pipeline and profile is None and dim == 3),
                    tail=tail, SP0=SP0, split0=bool(SP0 == 4 and tan0_rowsum), mult=mult)
 
     def plan_chunk(self, points):
@@ -661,7 +683,8 @@ def _gather_nd_desc(call, latent, Pc, p0, nt):
 
 def _forward_chunk(call, packs, packs16, latent, pts_c, jets, p0, need_grad=True):
     """Run gather + layers 1..5 + reduce for points [p0, p0+Pc) ; returns the buffers backward needs."""
-    nd = call.plan.dim != 3       # value query on a 1-, 2- or 4-d grid: own gather / corner sum, the same layer kernels
+    nd = call.plan.dim != 3       # query on a 1-, 2- or 4-d grid: own gather / corner sum, the same layer kernels
+    nd_jet = nd and call.S_out > 1    # ... with derivative streams (dim = 1, 2, ``nd_jets``; lig_jets let nothing else through)
     if call.pipeline:
         return _forward_chunk_c(call, packs, packs16, latent, pts_c, jets, p0, need_grad)
     plan, cfg, S = call.plan, call.cfg, call.S
@@ -679,6 +702,10 @@ def _forward_chunk(call, packs, packs16, latent, pts_c, jets, p0, need_grad=True
         gd = _gather_nd_desc(call, latent, Pc, p0, nt)
         with _timed("gather_nd"):
             check(L.stpde_lig_gather_nd(C.byref(gd), ptr(pts_c), ptr(latent), ptr(X), ptr(roww), st))
+        if nd_jet:
+            coef = torch.empty(Pc * 16, device=dev)
+            with _timed("coef_nd"):
+                check(L.stpde_lig_coef_nd(C.byref(gd), ptr(pts_c), ptr(coef), st))
     else:
         coef = torch.empty(Pc * 16, device=dev)
         cell = torch.empty(Pc, device=dev, dtype=torch.int32)
@@ -729,6 +756,12 @@ def _forward_chunk(call, packs, packs16, latent, pts_c, jets, p0, need_grad=True
                                         ptr(z0) if l == 1 else None, st))
         bufs.append(out)
         prev = out
+    if nd_jet:
+        # forward only (lig_jets refuses a derivative request that needs a gradient): no stash
+        with _timed("reduce_nd_jet"):
+            check(L.stpde_lig_reduce_nd_jet_fwd(C.byref(call.cfg_out), S, plan.dim, Pc, nt, plan.cout, ptr(bufs[5]), ptr(coef),
+                                                C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2], st))
+        return None
     if nd:
         with _timed("reduce_nd"):
             check(L.stpde_lig_reduce_nd_fwd(plan.dim, Pc, nt, plan.cout, ptr(bufs[5]), ptr(roww),
@@ -925,7 +958,8 @@ def _per_point_bytes(call):
     if call.packed_mask:
         bwd_tile += 4 * (_adj_floats(call, 1, 1) + _adj_floats(call, 4, 1) + _adj_floats(call, 0, 1))
     if plan.dim != 3:
-        fwd = fwd_tile * rows // 16 + 4 * rows                     # + the corner weight of every row
+        # + the corner weight of every row (+ the coefficient record of a derivative request)
+        fwd = fwd_tile * rows // 16 + 4 * rows + (4 * 16 if call.S_out > 1 else 0)
         bwd = bwd_tile * rows // 16 + rows * cp * 4 + 4 + 4 + 24   # per-row latent adjoints, cell id, permutation, sort scratch
         return fwd, bwd
     fwd = fwd_tile // 2 + 4 * 16 + (4 * 8 if call.cfg_out.combo else 0) + 4
@@ -980,10 +1014,12 @@ def _recompute_chunk(call, device):
 
 
 def _nd_chunk_points(call, device):
-    """Default launch chunk of a value-only query on a dim-d grid (dim = 1, 2, 4), in points: the row tiles of the dim = 3
-    default chunk, cut down (to a power of two) until one chunk's buffers -- X, the five layer buffers, the row weights --
-    take at most half of the call's memory budget / of the free device memory."""
-    tile_bytes = 4 * (sum(_buf_floats(call, l, 1) for l in range(1, 6)) + XT * _FRAG + 16)
+    """Default launch chunk of a query on a dim-d grid (dim = 1, 2, 4), in points: the row tiles of the dim = 3 default chunk,
+    cut down (to a power of two) until one chunk's buffers -- X, the five layer buffers with all ``call.S`` streams of the
+    request, the row weights, the coefficient records of a derivative request -- take at most half of the call's memory
+    budget / of the free device memory."""
+    tile_bytes = 4 * (sum(_buf_floats(call, l, 1) for l in range(1, 6)) + XT * _FRAG + 16
+                      + (16 * (16 >> call.plan.dim) if call.S_out > 1 else 0))
     tiles = DEFAULT_CHUNK // 2
     fit = max(4, int(0.5 * _avail_bytes(call, device) / tile_bytes))
     tiles = min(tiles, 1 << (fit.bit_length() - 1))
@@ -1193,6 +1229,9 @@ def set_mlp_precision(precision):
     return prev
 
 
+_ND_VALUE_ONLY = "dim = %d queries run in HIP as value-only forward passes (no coordinate derivatives)"
+
+
 def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), chunk_points=None, combo=None,
              precision=None, memory_budget=None):
     """HIP evaluation of y and its coordinate derivatives.
@@ -1215,19 +1254,25 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
     grids is always the deterministic per-node sum (``deterministic_dlatent = False`` is ignored; there is no atomic variant),
     the one-call pipeline (``use_pipeline``) stays dim = 3 only, and there are no coordinate derivatives and no point
     gradients (query_pts is detached).  Everything else on such grids is the composed formulation of local_implicit_grid.py.
+
+    imnet.dim = 1 or 2 with ``nd_jets`` (``set_nd_jets(True)`` / STPDE_ND_JETS=1): ``first`` / ``pairs`` (indices < dim) are
+    served as well, for calls that need no gradient: stpde_lig_coef_nd and stpde_lig_reduce_nd_jet_fwd around the layer
+    kernels in the request's stream set.  Returns (jets [1 + 3 + len(padded pairs), n_out, b*p], padded pairs) in the
+    dim = 3 stream order; the streams d/dq_k, k >= dim, are +0.0.  Refused: ``combo``, a call that needs a gradient, bf16
+    operands, dim = 4.
     """
     if not (latent_grid.is_cuda and query_pts.is_cuda):
         raise RuntimeError("the HIP jet path needs CUDA/HIP tensors (no CPU fallback)")
     dim = imnet.dim
+    wants_jets = bool(first or len(pairs) or combo)
     if dim == 3:
         if latent_grid.dim() != 5 or query_pts.dim() != 3 or query_pts.shape[-1] != 3:
             raise ValueError("lig_jets expects latent_grid [b,n0,n1,n2,c] and query_pts [b,p,3]")
     elif dim in ND_VALUE_DIMS:
         if latent_grid.dim() != dim + 2 or query_pts.dim() != 3 or query_pts.shape[-1] != dim:
             raise ValueError("lig_jets expects latent_grid [b,n_1..n_%d,c] and query_pts [b,p,%d]" % (dim, dim))
-        if first or len(pairs) or combo:
-            raise NotImplementedError("dim = %d queries run in HIP as value-only forward passes (no coordinate derivatives)"
-                                      % dim)
+        if wants_jets and dim not in ND_JET_DIMS:
+            raise NotImplementedError(_ND_VALUE_ONLY % dim)
         if min(latent_grid.shape[1:-1]) < 2:
             raise ValueError("every axis of the latent grid needs at least 2 nodes")
     else:
@@ -1257,6 +1302,17 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
     grid_shape = tuple(latent_grid.shape[1:-1])
     call = JetCall.make(plan, act, prm, first, pairs, combo, precision, grid_shape, cached_box_constants(grid_shape, xmin, xmax),
                         memory_budget, B, N, chunk_points, need_grad)
+    if dim != 3 and wants_jets:
+        # dim = 1, 2: whether derivative requests are served is one of the call's frozen switches
+        if not call.nd_jets:
+            raise NotImplementedError(_ND_VALUE_ONLY % dim)
+        if combo:
+            raise NotImplementedError("dim = %d: the combined second-order stream is dim = 3 only (ask for the pairs)" % dim)
+        if any(not (0 <= a < dim and 0 <= b < dim) for a, b in pairs):
+            raise ValueError("dim = %d: second-derivative pairs %r name an axis the grid does not have" % (dim, list(pairs)))
+        if need_grad:
+            raise NotImplementedError("dim = %d coordinate derivatives run in HIP as forward passes only: call under "
+                                      "torch.no_grad() or without inputs / parameters that require grad" % dim)
     P = B * N
     if P == 0:   # empty query set: nothing to launch (the reference returns an empty [b, 0, o] tensor as well)
         return torch.zeros(call.S_out, plan.cout, 0, device=query_pts.device), call.pairs

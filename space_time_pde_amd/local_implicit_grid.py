@@ -8,6 +8,8 @@ gather -> MLP -> corner-weighted sum, INCLUDING the coordinate derivatives, runs
 Value-only queries on 1-, 2- and 4-d grids (no jet request, nothing that needs a gradient) run in HIP as well: a gather and
 a corner sum of their own around the same IM-NET layer kernels (``_nd_value_eligible``).  With ``lig_jet.nd_backward``
 (opt-in) such a query also trains in HIP: gradients w.r.t. the latent grid and the IM-NET parameters (``_nd_train_eligible``).
+With ``lig_jet.nd_jets`` (opt-in) a PDE layer's derivative request on a 1- or 2-d grid that needs no gradient is answered by
+the HIP jet kernels too (``_nd_jet_eligible``).
 Other decoders / dimensions / requests use the generic composed formulation.
 """
 import threading
@@ -108,6 +110,23 @@ def _nd_train_eligible(model, latent_grid, query_pts, req=None):
     return bool(latent_grid.requires_grad or any(p.requires_grad for p in model.parameters()))
 
 
+def _nd_jet_eligible(model, latent_grid, query_pts, req=None):
+    """A query on a 1- or 2-d grid whose COORDINATE DERIVATIVES the HIP path serves (opt-in: ``lig_jet.nd_jets``,
+    ``lig_jet.set_nd_jets`` / STPDE_ND_JETS=1; off, this is always False and such a request is composed, as before): an active
+    jet request for exactly these points, without a combined second-order stream and with pair indices < d; everything
+    ``_nd_value_eligible`` asks for other than its request clause (ImNet decoder, CUDA fp32, nf a multiple of 16, out_features
+    <= 16, d + in_features + 1 <= 36, every axis >= 2 nodes, fp32 or fp32x3 operands); and nothing that needs a gradient
+    (no_grad, or no point / latent grid / parameter requiring grad): the adjoint of the derivative streams on these grids is
+    not built.  d = 4, point gradients and training through residuals keep the composed formulation."""
+    if not lig_jet.nd_jets or req is None or req.x is not query_pts or req.combo:
+        return False
+    if not isinstance(model, ImNet) or model.dim not in lig_jet.ND_JET_DIMS:
+        return False
+    if any(not (0 <= a < model.dim and 0 <= b < model.dim) for a, b in req.pairs):
+        return False
+    return _nd_value_eligible(model, latent_grid, query_pts, None)     # (its gradient clause included)
+
+
 def _xmin_is_zero(xmin, xmax=None, shape3=None):
     """The HIP kernels reproduce the reference's cell index, which ignores xmin (quirk a-Q1), for xmin == 0 only; any
     other lower bound takes the generic formulation, which behaves like the reference on every device.  Tensor bounds
@@ -192,6 +211,12 @@ def query_local_implicit_grid(model, latent_grid, query_pts, xmin, xmax):
             jets, _ = lig_jet.lig_jets(model, latent_grid, query_pts, xmin, xmax, False, ())
             stats["hip_value_calls"] += 1
             return jets[0].t().reshape(query_pts.shape[0], query_pts.shape[1], jets.shape[1])
+    if _nd_jet_eligible(model, latent_grid, query_pts, req) and _xmin_is_zero(xmin, xmax, tuple(latent_grid.shape[1:-1])):
+        jets, pairs = lig_jet.lig_jets(model, latent_grid, query_pts, xmin, xmax, req.first, req.pairs)
+        stats["hip_jet_calls"] += 1
+        y = jets[0].t().reshape(query_pts.shape[0], query_pts.shape[1], jets.shape[1])
+        req.y, req.jets, req.pairs_out = y, jets, pairs
+        return y
     if (_nd_value_eligible(model, latent_grid, query_pts, req) or _nd_train_eligible(model, latent_grid, query_pts, req)) \
             and _xmin_is_zero(xmin, xmax, tuple(latent_grid.shape[1:-1])):
         jets, _ = lig_jet.lig_jets(model, latent_grid, query_pts, xmin, xmax, False, ())

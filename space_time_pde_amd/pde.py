@@ -363,11 +363,20 @@ class PDELayer(object):
     def _jet_request(self, x):
         if not (self.eqns_jet and all(p is not None for p in self.eqns_jet.values())):
             return None
-        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 3 and self.n_in == 3):
+        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 3):
+            return None
+        nd = self.n_in in _lig.lig_jet.ND_JET_DIMS
+        if nd:
+            # 1- and 2-d problems (opt-in, ``lig_jet.nd_jets``): the HIP jets there serve forward passes that need no
+            # gradient, so a request is made with grad mode off only -- with it on the forward would be evaluated for the
+            # request, find it unserved and be evaluated again by the reverse sweeps
+            if not _lig.lig_jet.nd_jets or torch.is_grad_enabled():
+                return None
+        elif self.n_in != 3:
             return None
         if x.requires_grad and torch.is_grad_enabled():
             return None   # the caller wants autograd through the coordinates: only the generic strategy provides it
-        plan = self._combo_plan()
+        plan = None if nd else self._combo_plan()      # (the combined second-order stream is dim = 3 only: pairs there)
         if plan is not None:
             return _lig.JetRequest(x, True, [], combo=plan["alpha"])
         first, pairs = False, set()
@@ -430,6 +439,8 @@ class PDELayer(object):
             return None
         prog_t, nins, uses_x = ent
         x2d = x.detach().reshape(-1, self.n_in).contiguous().float() if uses_x else None
+        if x2d is not None and self.n_in < 3:      # the evaluator addresses x as [P][3]
+            x2d = torch.nn.functional.pad(x2d, (0, 3 - self.n_in)).contiguous()
         res = _ResidualHip.apply(jets, x2d, prog_t, nins, len(progs))
         return {name: res[k].reshape(shape) for k, name in enumerate(progs)}
 

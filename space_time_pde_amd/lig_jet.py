@@ -574,31 +574,98 @@ def _flags(call, need_grad, need_wgrad=True):
     return sum(bit for on, bit in bits if on)
 
 
-def _dlatent_scratch(call, rows, Pc, dev):
-    """Scratch of one chunk's deterministic d latent -> (adjoints of ``rows`` rows, permutation of the Pc points sorted by cell,
-    first sorted point of every grid node, temporary storage of the sort in bytes, number of nodes)."""
-    n_nodes = call.B * math.prod(call.grid_shape)
-    nb = int(_lib.lib().stpde_lig_sort_tmp_bytes(Pc, n_nodes))
-    return (torch.empty(rows * ((call.plan.cin + 3) // 4 * 4), device=dev), torch.empty(Pc, device=dev, dtype=torch.int32),
-            torch.empty(n_nodes + 1, device=dev, dtype=torch.int32), torch.empty(nb, device=dev, dtype=torch.uint8), n_nodes)
+def nd_tiles(P, dim):
+    """Row tiles of P points of a value query on a dim-d grid (dim = 1, 2, 4): 16 >> dim points per tile, rounded up to
+    the four tiles of one value-tile pass.  Rows past the last point are padding (zeros, weight 0: stpde_lig_gather_nd)."""
+    tp = 16 >> dim
+    return (-(-P // tp) + 3) // 4 * 4
+
+
+# ------------------------------------------------------------------------------------------------------------
+# THE table of the device buffers one launch chunk owns: [(name, elements, dtype)] in the order they are allocated.  The four
+# chunk drivers allocate from it (``_alloc``) and the memory plan sums it (``_per_point_bytes`` ...): a buffer is allocated and
+# counted, or neither.  The one-call and the per-kernel driver differ in the order (the caching allocator, and with it the
+# peak, sees it): the ``_ORDER`` rows, keyed by ``call.pipeline``.
+# ------------------------------------------------------------------------------------------------------------
+_LAYER_BUFS = tuple("buf%d" % l for l in range(1, 6))
+_FWD_ORDER = {True: ("X", "cw", "coef", "cell") + _LAYER_BUFS + ("z0",),
+              False: ("X", "cw", "roww", "coef", "cell", "buf1", "z0") + _LAYER_BUFS[1:]}
+_BWD_ORDER = {True: ("abar2x", "abar3x", "abar1x", "abar4x", "abar0x", "tan0", "abar0"),
+              False: ("abar0", "abar0x", "tan0", "abar1x", "abar4x", "abar3x", "abar2x")}
+_DTYPES = dict(cell=torch.int32, perm=torch.int32, start=torch.int32, sort_tmp=torch.uint8)     # every other one: fp32
+# the one size the PLAN estimates: 24 bytes per point for the temporary storage of the cell sort.  What is allocated is the
+# library's own answer (stpde_lig_sort_tmp_bytes), and asking for it needs the library.
+SORT_TMP_PLAN_BYTES = 24
+
+
+def _table(order, size):
+    """the buffers of ``order`` that exist (size[name] is not None)"""
+    return [(k, size[k], _DTYPES.get(k, torch.float32)) for k in order if size.get(k) is not None]
+
+
+def _chunk_tiles(call, Pc):
+    return nd_tiles(Pc, call.plan.dim) if call.plan.dim != 3 else Pc // 2
+
+
+def _forward_buffers(call, Pc, need_grad=True):
+    """Forward chunk: the fragment image X of the augmented input, what the gather records per point (dim = 3: row weights of
+    a combined second-order stream, interpolation coefficients, cell index; dim = 1, 2, 4: the corner weight of every row, and
+    coefficients for a derivative request only), the five layer buffers, and -- a backward can follow -- the value stream z0
+    of the layer-0 pre-activations."""
+    nd, nt = call.plan.dim != 3, _chunk_tiles(call, Pc)
+    size = dict(X=nt * XT * _FRAG, cw=Pc * 8 if call.cfg_out.combo else None, roww=nt * 16 if nd else None,
+                coef=Pc * 16 if (not nd or call.S_out > 1) else None, cell=None if nd else Pc,
+                z0=nt * call.plan.layers[0]["MT"] * _FRAG if need_grad else None)
+    size.update(("buf%d" % l, _buf_floats(call, l, nt)) for l in range(1, 6))
+    return _table(_FWD_ORDER[call.pipeline], size)
+
+
+def _backward_buffers(call, Pc):
+    """Backward chunk, the adjoints that do not go over a stash: fresh ones for layers 2 and 3 (one-call path: always;
+    per-kernel path: for the fused fc3 -> fc5 chain), the packed ADJOINT buffers of the bf16 mode (a format of their own), and
+    for layer 0 with tangent streams their row sums ``tan0`` or -- ``tan0_rowsum = False`` -- the full four-stream adjoint."""
+    nt, mt0, pk = _chunk_tiles(call, Pc), call.plan.layers[0]["MT"], call.packed_mask
+    on = {2: call.pipeline or call.tail, 3: call.pipeline or call.tail, 1: pk, 4: pk, 0: pk & 1}
+    size = {"abar%dx" % l: _adj_floats(call, l, nt) for l in on if on[l]}
+    size["tan0"] = nt * mt0 * 48 if call.split0 else None
+    size["abar0"] = nt * call.SP0 * mt0 * _FRAG if (call.SP0 == 4 and not call.split0) else None
+    return _table(_BWD_ORDER[call.pipeline], size)
+
+
+def _dlatent_buffers(call, Pc, estimate=False):
+    """Scratch of d latent as a per-node sum in a fixed order (dim = 3: ``det_dlatent``; dim = 1, 2, 4: always, with the cell
+    ids the forward does not keep there): the latent adjoint of every row (dim = 1, 2, 4: of all 16 rows of every tile,
+    k_xbar writes the padding rows too), the permutation of the points sorted by cell, the first sorted point of every grid
+    node, the temporary storage of the sort (``estimate``: what the plan counts for it)."""
+    nd = call.plan.dim != 3
+    if not (nd or call.det_dlatent):
+        return []
+    rows, n_nodes = 16 * _chunk_tiles(call, Pc) if nd else 8 * Pc, call.B * math.prod(call.grid_shape)
+    tmp = SORT_TMP_PLAN_BYTES * Pc if estimate else int(_lib.lib().stpde_lig_sort_tmp_bytes(Pc, n_nodes))
+    size = dict(xrows=rows * ((call.plan.cin + 3) // 4 * 4), perm=Pc, start=n_nodes + 1, sort_tmp=tmp, cell=Pc if nd else None)
+    return _table(("xrows", "perm", "start", "sort_tmp", "cell"), size)
+
+
+def _two_phase_buffers(call, Pc):
+    """Extras of the dgrad-first order (one-call path: tiles of 2 points): adjoint buffers of layers 1 and 0 of their own, which
+    the packed mode has anyway"""
+    return _table(("abar1x", "abar0x"), {"abar%dx" % l: _adj_floats(call, l, Pc // 2)
+                                         for l in (1, 0) if not (call.packed_mask >> l) & 1})
+
+
+def _alloc(table, dev):
+    """{name: tensor} of a table on ``dev``, allocated in the table's order"""
+    return {name: torch.empty(n, device=dev, dtype=dtype) for name, n, dtype in table}
 
 
 def _forward_chunk_c(call, packs, packs16, latent, pts_c, jets, p0, need_grad=True):
     """_forward_chunk through ONE library call: this function only allocates the chunk's buffers."""
     Pc = pts_c.shape[0]
-    nt = Pc // 2
-    dev = pts_c.device
+    s = _alloc(_forward_buffers(call, Pc, need_grad), pts_c.device)
+    s["bufs"] = [None] + [s.pop(name) for name in _LAYER_BUFS]
     ws = LigWorkspace()
-    s = dict(p0=p0, Pc=Pc, ws=ws)
-    s["X"] = torch.empty(nt * XT * _FRAG, device=dev)
-    s["XR"] = None      # (round 5: no row-major copy of X any more -- the weight-gradient kernels transpose the fragments they need)
-    s["cw"] = torch.empty(Pc * 8, device=dev) if call.cfg_out.combo else None
-    s["coef"] = torch.empty(Pc * 16, device=dev)
-    s["cell"] = torch.empty(Pc, device=dev, dtype=torch.int32)
-    s["bufs"] = [None] + [torch.empty(_buf_floats(call, l, nt), device=dev) for l in range(1, 6)]
-    s["z0"] = torch.empty(nt * call.plan.layers[0]["MT"] * _FRAG, device=dev) if need_grad else None
-    ws.X, ws.XR, ws.coef, ws.cw, ws.cell = (_dp(s[k]) for k in ("X", "XR", "coef", "cw", "cell"))
-    ws.pre[0] = _dp(s["z0"])
+    ws.X, ws.coef, ws.cw, ws.cell = (_dp(s.get(k)) for k in ("X", "coef", "cw", "cell"))
+    ws.pre[0] = _dp(s.get("z0"))
     for l in range(1, 6):
         ws.pre[l] = s["bufs"][l].data_ptr()
     pd = _plan_desc(call, packs, packs16)
@@ -606,7 +673,7 @@ def _forward_chunk_c(call, packs, packs16, latent, pts_c, jets, p0, need_grad=Tr
     check(_lib.lib().stpde_lig_imnet_jet_fwd(C.byref(pd), C.byref(call.cfg), C.byref(call.cfg_out), C.byref(gd), ptr(pts_c),
                                              ptr(latent), C.byref(ws), C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2],
                                              _flags(call, need_grad), stream_ptr()))
-    s["gd"] = gd
+    s.update(p0=p0, Pc=Pc, ws=ws, gd=gd)
     return s
 
 
@@ -619,32 +686,16 @@ def _backward_chunk_c(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, p
     current stream.  Round 4's variant with phase B on a side stream, so that the U-Net backward ran beside it, measured slower
     -- profiles/r4_overlap_timeline.txt -- and was deleted in round 6.)"""
     Pc, ws, gd = saved["Pc"], saved["ws"], saved["gd"]
-    nt = Pc // 2
-    dev = saved["X"].device
-    keep = []
-
-    def buf(n, dtype=torch.float32):
-        t = torch.empty(n, device=dev, dtype=dtype)
-        keep.append(t)
-        return t.data_ptr()
-
-    MT0 = call.plan.layers[0]["MT"]
-    ws.abar2x, ws.abar3x = buf(_adj_floats(call, 2, nt)), buf(_adj_floats(call, 3, nt))
-    if call.packed_mask:        # packed ADJOINT buffers are a format of their own: none of them goes over a stash
-        ws.abar1x, ws.abar4x = buf(_adj_floats(call, 1, nt)), buf(_adj_floats(call, 4, nt))
-        if call.packed_mask & 1:
-            ws.abar0x = buf(_adj_floats(call, 0, nt))
-    ws.tan0 = buf(nt * MT0 * 48) if call.split0 else None
-    ws.abar0 = buf(nt * call.SP0 * MT0 * _FRAG) if (call.SP0 == 4 and not call.split0) else None
-    if dlatent is not None and call.det_dlatent:
-        scratch = _dlatent_scratch(call, Pc * 8, Pc, dev)[:4]
-        keep += scratch
-        ws.xrows, ws.perm, ws.start, ws.sort_tmp = (t.data_ptr() for t in scratch)
-        ws.sort_tmp_bytes = scratch[3].numel()
-    pd = _plan_desc(call, packs, packs16)
-    flags = _flags(call, True, dw_flat is not None)
     # (the stream sets of ``tail`` have SP0 = 1 or 4, what the two-phase order is compiled for)
     two_phase = after_dlatent is not None and call.tail and call.tan0_rowsum
+    scratch = _alloc(_backward_buffers(call, Pc) + (_dlatent_buffers(call, Pc) if dlatent is not None else [])
+                     + (_two_phase_buffers(call, Pc) if two_phase else []), saved["X"].device)
+    for name, t in scratch.items():         # (the table's names are the workspace's)
+        setattr(ws, name, t.data_ptr())
+    if "sort_tmp" in scratch:
+        ws.sort_tmp_bytes = scratch["sort_tmp"].numel()
+    pd = _plan_desc(call, packs, packs16)
+    flags = _flags(call, True, dw_flat is not None)
 
     def launch(fl):
         check(_lib.lib().stpde_lig_imnet_jet_bwd(C.byref(pd), C.byref(call.cfg), C.byref(call.cfg_out), C.byref(call.cfg_val),
@@ -652,10 +703,6 @@ def _backward_chunk_c(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, p
                                                  jets_bar.shape[2], ptr(dw_flat), ptr(dlatent), ptr(pbar), fl, stream_ptr()))
 
     if two_phase:
-        if not call.packed_mask:
-            ws.abar1x = buf(saved["bufs"][1].numel())
-        if not call.packed_mask & 1:
-            ws.abar0x = buf(nt * MT0 * _FRAG)
         launch(flags | _lib.F_PHASE_A)
         after_dlatent()
         launch(flags | _lib.F_PHASE_B)
@@ -663,14 +710,6 @@ def _backward_chunk_c(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, p
         launch(flags)
         if after_dlatent is not None:
             after_dlatent()
-    return None
-
-
-def nd_tiles(P, dim):
-    """Row tiles of P points of a value query on a dim-d grid (dim = 1, 2, 4): 16 >> dim points per tile, rounded up to
-    the four tiles of one value-tile pass.  Rows past the last point are padding (zeros, weight 0: stpde_lig_gather_nd)."""
-    tp = 16 >> dim
-    return (-(-P // tp) + 3) // 4 * 4
 
 
 def _gather_nd_desc(call, latent, Pc, p0, nt):
@@ -688,35 +727,26 @@ def _forward_chunk(call, packs, packs16, latent, pts_c, jets, p0, need_grad=True
     if call.pipeline:
         return _forward_chunk_c(call, packs, packs16, latent, pts_c, jets, p0, need_grad)
     plan, cfg, S = call.plan, call.cfg, call.S
-    L = _lib.lib()
-    st = stream_ptr()
+    L, st = _lib.lib(), stream_ptr()
     Pc = pts_c.shape[0]
-    nt = nd_tiles(Pc, plan.dim) if nd else Pc // 2
-    dev = pts_c.device
-    X = torch.empty(nt * XT * _FRAG, device=dev)
-    XR = None           # (round 5: no row-major copy of X; the weight-gradient kernels read X)
-    cw = torch.empty(Pc * 8, device=dev) if call.cfg_out.combo else None
-    coef = cell = roww = None
+    nt = _chunk_tiles(call, Pc)
+    s = _alloc(_forward_buffers(call, Pc, need_grad), pts_c.device)
+    bufs = s["bufs"] = [None] + [s.pop(name) for name in _LAYER_BUFS]
+    # (z0 is kept for the layer-1 input-gradient kernel, which then writes the layer-0 adjoint over it: reading 2 KB per row
+    # back is cheaper than regenerating it on the fp32 MFMA)
+    X, cw, coef, cell, roww, z0 = (s.get(k) for k in ("X", "cw", "coef", "cell", "roww", "z0"))
     if nd:
-        roww = torch.empty(nt * 16, device=dev)       # corner weight of every row (cw of stpde_lig_gather_nd)
         gd = _gather_nd_desc(call, latent, Pc, p0, nt)
         with _timed("gather_nd"):
             check(L.stpde_lig_gather_nd(C.byref(gd), ptr(pts_c), ptr(latent), ptr(X), ptr(roww), st))
         if nd_jet:
-            coef = torch.empty(Pc * 16, device=dev)
             with _timed("coef_nd"):
                 check(L.stpde_lig_coef_nd(C.byref(gd), ptr(pts_c), ptr(coef), st))
     else:
-        coef = torch.empty(Pc * 16, device=dev)
-        cell = torch.empty(Pc, device=dev, dtype=torch.int32)
         gd = _gather_desc(call, latent, Pc, p0)
         with _timed("gather"):
-            check(L.stpde_lig_gather(C.byref(gd), ptr(pts_c), ptr(latent), ptr(X), ptr(XR), ptr(coef), ptr(cell),
-                                     ptr(cw), st))
-    bufs = [None]
+            check(L.stpde_lig_gather(C.byref(gd), ptr(pts_c), ptr(latent), ptr(X), None, ptr(coef), ptr(cell), ptr(cw), st))
     pv = plan.pack_view
-    prev = None
-    z0 = None
     # forward-only value queries (inference): VALUE-TILE kernels -- four consecutive row tiles share one pass over the
     # weights (the weight operand is what bounds a one-stream pass); same buffers, a quarter of the "tiles"
     vt = S == 1 and not need_grad and (not packs16 or call.nsplit == 3) and nt % 4 == 0 and call.value_tiles
@@ -730,51 +760,40 @@ def _forward_chunk(call, packs, packs16, latent, pts_c, jets, p0, need_grad=True
     for l in range(1, 6):
         lay = plan.layers[l]
         if tail and l == 3:
-            outs = [torch.empty(_buf_floats(call, k, nt), device=dev) for k in (3, 4, 5)]
             arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
             pk_tail = (call.packed_mask >> 2) & 1         # bf16 mode: packed buffers on both sides, bf16-operand kernel
             w16s = arr([packs16[(k, "Wh")] for k in (3, 4, 5)]) if pk_tail else None
             with _timed("tail_fwd"):
-                check(L.stpde_jet_tail_fwd_p(C.byref(lcfg), lnt, plan.nf // 16, ptr(prev), ptr(X),
+                check(L.stpde_jet_tail_fwd_p(C.byref(lcfg), lnt, plan.nf // 16, ptr(bufs[2]), ptr(X),
                                              arr([pv(packs, k, "Wh") for k in (3, 4, 5)]),
                                              arr([pv(packs, k, "Ws") for k in (3, 4, 5)]),
-                                             arr([pv(packs, k, "tanc") for k in (3, 4, 5)]), arr(outs), ptr(cw),
+                                             arr([pv(packs, k, "tanc") for k in (3, 4, 5)]), arr(bufs[3:6]), ptr(cw),
                                              3 if pk_tail else 0, w16s, st))
-            bufs += outs
             break
-        out = torch.empty(_buf_floats(call, l, nt), device=dev)
         w16 = packs16.get((l, "Wh")) if packs16 else None
         d = _layer_desc(call, lnt, lay, lcfg, l == 1, call.nsplit if w16 is not None else 0, _pk(call, l, l) & 3)
-        if l == 1 and need_grad:
-            # value stream of the layer-0 pre-activations, kept for the layer-1 input-gradient kernel (which then writes
-            # the layer-0 adjoint over it): reading 2 KB per row back is cheaper than regenerating it on the fp32 MFMA
-            z0 = torch.empty(nt * plan.layers[0]["MT"] * _FRAG, device=dev)
         with _timed("layer%d_fwd" % l):
-            check(L.stpde_jet_layer_fwd(C.byref(d), ptr(prev), ptr(X), ptr(pv(packs, l, "Wh")),
+            check(L.stpde_jet_layer_fwd(C.byref(d), ptr(bufs[l - 1]), ptr(X), ptr(pv(packs, l, "Wh")),
                                         ptr(pv(packs, l, "Ws")), ptr(pv(packs, l, "tanc")), ptr(pv(packs, 0, "Ws")),
-                                        ptr(pv(packs, 0, "tanc")), ptr(out), ptr(cw), ptr(w16),
+                                        ptr(pv(packs, 0, "tanc")), ptr(bufs[l]), ptr(cw), ptr(w16),
                                         ptr(z0) if l == 1 else None, st))
-        bufs.append(out)
-        prev = out
     if nd_jet:
-        # forward only (lig_jets refuses a derivative request that needs a gradient): no stash
         with _timed("reduce_nd_jet"):
             check(L.stpde_lig_reduce_nd_jet_fwd(C.byref(call.cfg_out), S, plan.dim, Pc, nt, plan.cout, ptr(bufs[5]), ptr(coef),
                                                 C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2], st))
-        return None
-    if nd:
+    elif nd:
         with _timed("reduce_nd"):
             check(L.stpde_lig_reduce_nd_fwd(plan.dim, Pc, nt, plan.cout, ptr(bufs[5]), ptr(roww),
                                             C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2], st))
-        if not need_grad:
-            return None
-        # training (``nd_backward``): the S = 1 layer configuration above kept z0; the backward needs the points again for
-        # the cell ids (stpde_lig_cell_nd) and the row weights for the adjoint of the corner sum
-        return dict(X=X, bufs=bufs, z0=z0, roww=roww, pts_c=pts_c, p0=p0, Pc=Pc, nt=nt)
-    with _timed("reduce_fwd"):
-        check(L.stpde_lig_reduce_fwd(C.byref(call.cfg_out), S, Pc, plan.cout, ptr(bufs[5]), ptr(coef),
-                                     C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2], st))
-    return dict(X=X, XR=X, coef=coef, cell=cell, bufs=bufs, p0=p0, Pc=Pc, cw=cw, z0=z0)
+    else:
+        with _timed("reduce_fwd"):
+            check(L.stpde_lig_reduce_fwd(C.byref(call.cfg_out), S, Pc, plan.cout, ptr(bufs[5]), ptr(coef),
+                                         C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2], st))
+    if nd and (nd_jet or not need_grad):    # no stash (lig_jets refuses a derivative request that needs a gradient)
+        return None
+    # (dim = 1, 2, 4, ``nd_backward``: the backward needs the points again, for the cell ids -- stpde_lig_cell_nd)
+    s.update(pts_c=pts_c, p0=p0, Pc=Pc)
+    return s
 
 
 def _backward_chunk(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pbar=None, after_dlatent=None):
@@ -787,13 +806,11 @@ def _backward_chunk(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pba
     if "ws" in saved:
         return _backward_chunk_c(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pbar, after_dlatent)
     plan, cfg, S = call.plan, call.cfg, call.S
-    L = _lib.lib()
-    st = stream_ptr()
-    Pc, p0 = saved["Pc"], saved["p0"]
-    nd = plan.dim != 3
-    nt = saved["nt"] if nd else Pc // 2
-    X, bufs = saved["X"], saved["bufs"]
-    XR, coef, cell, cw = (X, None, None, None) if nd else (saved[k] for k in ("XR", "coef", "cell", "cw"))
+    L, st = _lib.lib(), stream_ptr()
+    Pc, p0, nd = saved["Pc"], saved["p0"], plan.dim != 3
+    nt = _chunk_tiles(call, Pc)
+    X, bufs, z0 = saved["X"], saved["bufs"], saved["z0"]
+    coef, cell, cw = (saved.get(k) for k in ("coef", "cell", "cw"))
     dev = X.device
     pv = plan.pack_view
     SP0, split0, need_wgrad = call.SP0, call.split0, dw_flat is not None
@@ -809,18 +826,15 @@ def _backward_chunk(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pba
     # layer-0 adjoint: the value stream as fragment blocks; the three tangent streams only as per-tile row sums (their
     # layer-0 "input" is the constant column W0[:, d], so only sum_rows matters): 32 + 6 KB per tile instead of 128 KB
     MT0 = plan.layers[0]["MT"]
-    z0 = saved["z0"]
-    # the value-stream-only layer-0 adjoint goes over the z0 stash (same shape; each lane reads before it writes)
-    abar0 = z0 if (split0 or SP0 == 1) else torch.empty(nt * SP0 * MT0 * _FRAG, device=dev)
-    if call.packed_mask & 1:       # bf16 mode: packed ADJOINT buffer (bf16 blocks) of its own
-        abar0 = torch.empty(_adj_floats(call, 0, nt), device=dev)
-    tan0 = torch.empty(nt * MT0 * 48, device=dev) if split0 else None
+    adj = _alloc(_backward_buffers(call, Pc), dev)
+    # the value-stream-only layer-0 adjoint goes over the z0 stash (same shape; each lane reads before it writes); bf16 mode:
+    # a packed ADJOINT buffer (bf16 blocks) of its own
+    abar0, tan0 = adj.get("abar0x", adj.get("abar0", z0)), adj.get("tan0")
     # fc5 -> fc4 -> fc3 input gradients in one kernel (adjoints of layers 4 and 3 feed the next GEMM from the registers).
     # Order: wgrad_5 (needs the pre-activations of fc4's output intact), the chain (abar4 in place; abar3 / abar2 into
     # fresh buffers because wgrad_4 / wgrad_3 still need the pre-activations they would overwrite), wgrad_4, wgrad_3.
-    abar = {l: bufs[l] for l in range(1, 6)}      # where the adjoint of layer l's output rows lives once it exists
-    if call.packed_mask:           # packed ADJOINT buffers are a format of their own: none of them goes over a stash
-        abar[1], abar[4] = (torch.empty(_adj_floats(call, k, nt), device=dev) for k in (1, 4))
+    # abar[l]: where the adjoint of layer l's output rows lives once it exists -- over the stash, or in a buffer of its own
+    abar = {l: adj.get("abar%dx" % l, bufs[l]) for l in range(1, 6)}
     for l in range(5, 0, -1):
         lay = plan.layers[l]
         w16 = packs16.get((l, "WhT")) if packs16 else None
@@ -836,15 +850,14 @@ def _backward_chunk(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pba
             # (csrc/jet_fc1_bwd.hip: one read of the adjoint tile, one activation-jet evaluation per z0 element)
             with _timed("layer1_bwd"):
                 check(L.stpde_jet_fc1_bwd(C.byref(d), ptr(abar[1]), ptr(w16), ptr(z0), ptr(pv(packs, 0, "tanc")), ptr(cw),
-                                          ptr(XR), ptr(abar0), ptr(tan0), ptr(_dw_slice(call, dw_flat, 1)), ptr(pbar), st))
+                                          ptr(X), ptr(abar0), ptr(tan0), ptr(_dw_slice(call, dw_flat, 1)), ptr(pbar), st))
             continue
         if need_wgrad:
             with _timed("layer%d_wgrad" % l):
                 check(L.stpde_jet_wgrad(C.byref(dwg), S, ptr(abar[l]), ptr(bufs[l - 1]) if l > 1 else ptr(saved["z0"]),
-                                        ptr(XR), ptr(pv(packs, 0, "tanc")), ptr(_dw_slice(call, dw_flat, l)), ptr(cw), st))
+                                        ptr(X), ptr(pv(packs, 0, "tanc")), ptr(_dw_slice(call, dw_flat, l)), ptr(cw), st))
         if call.tail and l >= 3:
             if l == 5:
-                abar[3], abar[2] = (torch.empty(_adj_floats(call, k, nt), device=dev) for k in (3, 2))
                 arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
                 pk_tail = (call.packed_mask >> 2) & 1
                 w16s = (C.c_void_p * 3)(packs16[(3, "WhT")].data_ptr(), packs16[(4, "WhT")].data_ptr(), None) \
@@ -873,10 +886,10 @@ def _backward_chunk(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pba
         with _timed("layer0_wgrad"):
             if split0:
                 d.cfg = call.cfg_val      # value stream x raw input (the S = 1 weight-gradient kernels)
-                check(L.stpde_jet_wgrad(C.byref(d), 1, ptr(abar0), None, ptr(XR), None, ptr(dw0), None, st))
+                check(L.stpde_jet_wgrad(C.byref(d), 1, ptr(abar0), None, ptr(X), None, ptr(dw0), None, st))
                 check(L.stpde_jet_tan0_reduce(nt, MT0, ptr(tan0), ptr(dw0), plan.dw_off[0][2], int(call.det), st))
             else:
-                check(L.stpde_jet_wgrad(C.byref(d), SP0, ptr(abar0), None, ptr(XR), None, ptr(dw0), ptr(cw), st))
+                check(L.stpde_jet_wgrad(C.byref(d), SP0, ptr(abar0), None, ptr(X), None, ptr(dw0), ptr(cw), st))
     if dlatent is not None:
         xd = XbarDesc()
         xd.ntiles, xd.nlayers, xd.C = nt, 5, plan.cin
@@ -889,34 +902,30 @@ def _backward_chunk(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pba
             xd.packed[l], xd.S[l] = (call.packed_mask >> l) & 1, (S if l else 1)
             ab[l] = (abar0 if l == 0 else abar[l]).data_ptr()
             wt[l] = pv(packs, l, "WsL").data_ptr()
-        if nd:
-            # per-row adjoints for all 16 * nt rows (k_xbar writes the padding rows of the last tiles too), the cell id of
-            # every point, then the per-node sum over 2^dim corners in fixed order
-            xrows, perm, start, tmp, n_nodes = _dlatent_scratch(call, 16 * nt, Pc, dev)
-            cell = torch.empty(Pc, device=dev, dtype=torch.int32)
-            gd = _gather_nd_desc(call, dlatent, Pc, p0, nt)
-            with _timed("xbar_scatter"):
-                check(L.stpde_lig_xbar_rows(C.byref(xd), ab, wt, ptr(xrows), st))
-                check(L.stpde_lig_cell_nd(C.byref(gd), ptr(saved["pts_c"]), ptr(cell), st))
-                check(L.stpde_lig_cell_sort(Pc, n_nodes, ptr(cell), ptr(perm), ptr(start), ptr(tmp), tmp.numel(), st))
-                check(L.stpde_lig_dlatent_reduce_nd(plan.dim, call.B, (C.c_int * 4)(*call.grid_shape), plan.cin, ptr(xrows),
-                                                    ptr(perm), ptr(start), ptr(dlatent), st))
-        elif not call.det_dlatent:
+        if not (nd or call.det_dlatent):
             with _timed("xbar_scatter"):
                 check(L.stpde_lig_xbar_scatter(C.byref(xd), ab, wt, ptr(cell), ptr(dlatent), st))
         else:
-            # deterministic scatter: per-row adjoints, then a per-node gather in fixed order over the cell-sorted points
-            # (the same three library calls the one-call path makes, scratch allocated OUTSIDE the timed region: with torch.sort /
-            # index_add_ / cumsum in here the caching allocator's stalls showed up as a 60-75 ms "kernel" in bench.py's table)
-            xrows, perm, start, tmp, n_nodes = _dlatent_scratch(call, Pc * 8, Pc, dev)
+            # deterministic: per-row adjoints (dim = 1, 2, 4: and the cell id of every point), then a per-node sum in fixed order
+            # over the cell-sorted points -- the library calls of the one-call path, scratch allocated OUTSIDE the timed region
+            # (with torch.sort / index_add_ / cumsum in here the caching allocator's stalls showed up as a 60-75 ms "kernel")
+            sc = _alloc(_dlatent_buffers(call, Pc), dev)
+            xrows, perm, start, tmp = (sc[k] for k in ("xrows", "perm", "start", "sort_tmp"))
+            cell = sc.get("cell", cell)         # (dim = 1, 2, 4: the forward keeps no cell ids)
             with _timed("xbar_scatter"):
                 check(L.stpde_lig_xbar_rows(C.byref(xd), ab, wt, ptr(xrows), st))
-                check(L.stpde_lig_cell_sort(Pc, n_nodes, ptr(cell), ptr(perm), ptr(start), ptr(tmp), tmp.numel(), st))
-                check(L.stpde_lig_dlatent_reduce(call.B, call.grid_shape[0], call.grid_shape[1], call.grid_shape[2],
-                                                 plan.cin, ptr(xrows), ptr(perm), ptr(start), ptr(dlatent), st))
+                if nd:
+                    gd = _gather_nd_desc(call, dlatent, Pc, p0, nt)
+                    check(L.stpde_lig_cell_nd(C.byref(gd), ptr(saved["pts_c"]), ptr(cell), st))
+                check(L.stpde_lig_cell_sort(Pc, start.numel() - 1, ptr(cell), ptr(perm), ptr(start), ptr(tmp), tmp.numel(), st))
+                if nd:
+                    check(L.stpde_lig_dlatent_reduce_nd(plan.dim, call.B, (C.c_int * 4)(*call.grid_shape), plan.cin, ptr(xrows),
+                                                        ptr(perm), ptr(start), ptr(dlatent), st))
+                else:
+                    check(L.stpde_lig_dlatent_reduce(*((call.B,) + call.grid_shape), plan.cin, ptr(xrows), ptr(perm),
+                                                     ptr(start), ptr(dlatent), st))
     if after_dlatent is not None:      # per-kernel (profiling) path: weight gradients first, nothing left to overlap
         after_dlatent()
-    return None
 
 
 # {"dlatent": f(tensor) -> work | None, "dw": f(tensor) -> work | None}: collectives of the point-sharded step, started from
@@ -942,35 +951,23 @@ def _free_bytes(device):
     return free + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
 
 
+def _table_bytes(table):
+    return sum(n * dtype.itemsize for _, n, dtype in table)
+
+
 def _per_point_bytes(call):
-    """(forward stash, backward scratch) bytes per query point of the jet path, from the SAME size functions the chunk
-    allocators use (``_buf_floats`` / ``_adj_floats``: fp32 blocks or the packed formats of the bf16 mode), plus the
-    fragment images of the augmented input (X, XR), the interpolation coefficients, the per-row weights of a combined
-    second-order stream and the cell index.  A point owns 8 of a tile's 16 rows (tile = 2 points); on a dim = 1, 2, 4 grid
-    2^dim of them, i.e. 2^dim / 16 tiles, and the per-point extras are the row weights, the cell id and the sort scratch
-    (the up to 3 + 1 padding tiles of a chunk, ``nd_tiles``, are not counted: the plan keeps 15 % of headroom)."""
-    plan = call.plan
-    mt0 = plan.layers[0]["MT"]
-    cp = (plan.cin + 3) // 4 * 4
-    rows = 8 if plan.dim == 3 else 1 << plan.dim
-    fwd_tile = 4 * (sum(_buf_floats(call, l, 1) for l in range(1, 6)) + mt0 * _FRAG + XT * _FRAG)
-    bwd_tile = 4 * (_adj_floats(call, 2, 1) + _adj_floats(call, 3, 1) + mt0 * 48)
-    if call.packed_mask:
-        bwd_tile += 4 * (_adj_floats(call, 1, 1) + _adj_floats(call, 4, 1) + _adj_floats(call, 0, 1))
-    if plan.dim != 3:
-        # + the corner weight of every row (+ the coefficient record of a derivative request)
-        fwd = fwd_tile * rows // 16 + 4 * rows + (4 * 16 if call.S_out > 1 else 0)
-        bwd = bwd_tile * rows // 16 + rows * cp * 4 + 4 + 4 + 24   # per-row latent adjoints, cell id, permutation, sort scratch
-        return fwd, bwd
-    fwd = fwd_tile // 2 + 4 * 16 + (4 * 8 if call.cfg_out.combo else 0) + 4
-    bwd = bwd_tile // 2 + 8 * cp * 4 + 4 + 24          # per-row latent adjoints, permutation, radix-sort scratch
-    return fwd, bwd
+    """(forward stash, backward scratch) bytes per query point of the jet path: the chunk's buffer tables (``_forward_buffers``
+    with a stash; ``_backward_buffers`` + ``_dlatent_buffers``, the sort's temporary storage at the plan's estimate) for
+    ``call.mult`` points -- whole tiles, a point owns 8 of a tile's 16 rows, on a dim = 1, 2, 4 grid 2^dim -- over those points.
+    Not counted: the up to 3 + 1 padding tiles of a chunk on such a grid (``nd_tiles``; the plan keeps 15 % of headroom), and
+    ``start``, one int per grid node whatever the chunk."""
+    bwd = [b for b in _backward_buffers(call, call.mult) + _dlatent_buffers(call, call.mult, True) if b[0] != "start"]
+    return _table_bytes(_forward_buffers(call, call.mult)) // call.mult, _table_bytes(bwd) // call.mult
 
 
 def _two_phase_bytes(call):
     """extra bytes per point of the dgrad-first order (last chunk of a sharded_step backward): two more adjoint buffers"""
-    mt0 = call.plan.layers[0]["MT"]
-    return 2 * ((0 if call.packed_mask else _buf_floats(call, 1, 1)) + (0 if call.packed_mask & 1 else mt0 * _FRAG))
+    return _table_bytes(_two_phase_buffers(call, call.mult)) // call.mult
 
 
 # Device-memory budget of ONE jet call in bytes (None = whatever the device has free): a call whose forward stash + backward
@@ -1015,11 +1012,9 @@ def _recompute_chunk(call, device):
 
 def _nd_chunk_points(call, device):
     """Default launch chunk of a query on a dim-d grid (dim = 1, 2, 4), in points: the row tiles of the dim = 3 default chunk,
-    cut down (to a power of two) until one chunk's buffers -- X, the five layer buffers with all ``call.S`` streams of the
-    request, the row weights, the coefficient records of a derivative request -- take at most half of the call's memory
-    budget / of the free device memory."""
-    tile_bytes = 4 * (sum(_buf_floats(call, l, 1) for l in range(1, 6)) + XT * _FRAG + 16
-                      + (16 * (16 >> call.plan.dim) if call.S_out > 1 else 0))
+    cut down (to a power of two) until one chunk's forward buffers (``_forward_buffers``: all ``call.S`` streams of the request)
+    take at most half of the call's memory budget / of the free device memory."""
+    tile_bytes = _table_bytes(_forward_buffers(call, call.mult, call.need_grad)) // 4      # (call.mult points: 4 row tiles)
     tiles = DEFAULT_CHUNK // 2
     fit = max(4, int(0.5 * _avail_bytes(call, device) / tile_bytes))
     tiles = min(tiles, 1 << (fit.bit_length() - 1))

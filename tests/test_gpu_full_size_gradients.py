@@ -111,10 +111,9 @@ def _share_tiles():
 def _kept_points(meta):
     """Exactly KEEP point indices: both points of every edge tile, the rest drawn at random (seeded) over the whole launch."""
     from space_time_pde_amd import lig_jet
-    mt0 = meta.plan.layers[0]["MT"]
-    stash = max([lig_jet._buf_floats(meta, l, 1) for l in range(1, 6)] + [mt0 * lig_jet._FRAG, lig_jet.XT * lig_jet._FRAG])
-    adj_layers = (2, 3) + ((1, 4, 0) if meta.packed_mask else ())
-    adj = max(lig_jet._adj_floats(meta, l, 1) for l in adj_layers)
+    # the largest stash and the largest adjoint buffer of one row tile (2 points), from the table the drivers allocate from
+    stash = max(n for _, n, _ in lig_jet._forward_buffers(meta, 2))
+    adj = max(n for name, n, _ in lig_jet._backward_buffers(meta, 2) if name.startswith("abar"))
     fwd, bwd = lig_jet._per_point_bytes(meta)
     assert 4 * stash <= 2 * fwd and 4 * adj <= 2 * bwd        # both are buffers the memory plan accounts for (tile = 2 points)
     groups = {"first / last row tiles": {0, 1, NT - 2, NT - 1}, "persistent shares": _share_tiles()}

@@ -454,7 +454,7 @@ int stpde_lig_dlatent_reduce_nd(int D, int B, const int* n /* [D] on the host */
  * set (3, 0), (3, 2), (3, 4) or (3, 6) over ntiles row tiles of 16 >> D points, stpde_lig_reduce_nd_jet_fwd.  The layer
  * kernels carry three tangent streams whatever D is: the caller's `tanc` packs must hold zeros for the columns d >= D, which
  * makes the streams of those axes identically zero.  Not served (the caller keeps the composed formulation): D = 4, the
- * combined second-order stream (its per-row weights are indexed two points per tile), bf16 operands, and any backward.
+ * combined second-order stream (its per-row weights are indexed two points per tile) and bf16 operands; the backward is below.
  *   stpde_lig_coef_nd            coef[p][16] of stpde_lig_gather for point p of the chunk, from the same clip and cell index
  *                                as stpde_lig_gather_nd: {om[0][k], om[1][k], dom[0][k], dom[1][k], kap[k]} at 0 / 3 / 6 / 9 /
  *                                12 + k for k < D; om = 1, dom = 0, kap = 0 for the axes k >= D; entry 15 = 0.  Checks of
@@ -474,6 +474,34 @@ int stpde_lig_coef_nd(const stpde_gather_nd_desc* d, const float* pts, float* co
 int stpde_lig_reduce_nd_jet_fwd(const stpde_jet_cfg* cfg, int S_mlp, int D, int P, int ntiles, int n_out,
                                 const float* out_pre /* [ntiles][S_mlp][1][256] */, const float* coef,
                                 float* jets /* [S][n_out][ldp] */, long ldp, void* stream);
+
+/* ---- training through those derivatives (dim = 1, 2): the adjoint of stpde_lig_reduce_nd_jet_fwd ------------------------
+ * Between stpde_lig_reduce_nd_jet_bwd and the d latent calls of the value path (stpde_lig_xbar_rows on the value-stream
+ * adjoints, stpde_lig_cell_nd, stpde_lig_cell_sort, stpde_lig_dlatent_reduce_nd) runs the per-kernel backward of dim = 3 in
+ * the call's stream set over ntiles row tiles: stpde_jet_layer_bwd / _bwd_to, stpde_jet_tail_bwd_p, and the weight
+ * gradients through the two `_nd` entry points below.  What those kernels do with the tangent streams of the axes k >= D
+ * (all of them carry three): the forward streams are identically zero (`tanc` columns), their adjoints are exact zeros
+ * (stpde_lig_reduce_nd_jet_bwd writes +0.0, no pair names such an axis, so no activation-jet cross term feeds them), and
+ * the one place that would ADD something of theirs to a latent channel's weight column -- the row sums of tangent adjoint k
+ * into raw-input column k of a layer's weight-gradient block -- is told the number of coordinate axes.
+ *   stpde_lig_reduce_nd_jet_bwd  abar_out [ntiles][S_mlp][1][256] (over the forward's out_pre): lane (g, j), register r of
+ *                                tile t, stream s = the adjoint of output feature 4 g + r of row j, which belongs to point
+ *                                p = t * (16 >> D) + (j >> D), corner j & (2^D - 1); the coefficient algebra of
+ *                                stpde_lig_reduce_bwd.  EVERY float of the buffer is written: zeros for features >= n_out,
+ *                                for padding rows (p >= P) and for the tangent streams of the axes k >= D.  The rows
+ *                                jets_bar[1 + k], k >= D, are never read (the forward stored +0.0 there).  S_mlp < 1 + S1 +
+ *                                S2: the second-order cotangents still reach streams 0 .. 3 through the weight cross terms.
+ *                                Argument checks of stpde_lig_reduce_nd_jet_fwd; nothing is read for p >= P.
+ *   stpde_jet_wgrad_nd           stpde_jet_wgrad with ncoord = D coordinate axes (1 .. 3; 3 = stpde_jet_wgrad): the row sums
+ *                                of tangent-stream adjoint k are added to raw-input column k for k < ncoord only.  ncoord != 3
+ *                                with plain bf16 operands or packed buffers: STPDE_E_UNSUPPORTED.
+ *   stpde_jet_tan0_reduce_nd     stpde_jet_tan0_reduce likewise: columns k < ncoord only. */
+int stpde_lig_reduce_nd_jet_bwd(const stpde_jet_cfg* cfg, int S_mlp, int D, int P, int ntiles, int n_out,
+                                const float* jets_bar /* [S][n_out][ldp] */, long ldp, const float* coef,
+                                float* abar_out /* [ntiles][S_mlp][1][256] */, void* stream);
+int stpde_jet_wgrad_nd(const stpde_layer_desc* d, int SP, const float* abar_out, const float* in_pre, const float* X,
+                       const float* tanc0, float* dW_aug, const float* cw, int ncoord, void* stream);
+int stpde_jet_tan0_reduce_nd(int ntiles, int MT, const float* abar0_tan, float* dW_aug, int ldw, int det, int ncoord, void* stream);
 
 /* ---- a10: 3-D convolution of the U-Net encoder (src/unet3d.py:39-56: nn.Conv3d 1x1x1 and 3x3x3/pad 1, stride 1)
  * Activations are channels-last: x [B][T][Z][X][Ci], y [B][T][Z][X][Co], Ci and Co multiples of 16.

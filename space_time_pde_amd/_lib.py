@@ -253,6 +253,10 @@ _SIGNATURES = {
     "stpde_lig_coef_nd": ([C.POINTER(GatherNdDesc), _VP, _VP, _VP], C.c_int),
     "stpde_lig_reduce_nd_jet_fwd": ([C.POINTER(JetCfg), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, C.c_long,
                                      _VP], C.c_int),
+    "stpde_lig_reduce_nd_jet_bwd": ([C.POINTER(JetCfg), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, C.c_long, _VP, _VP,
+                                     _VP], C.c_int),
+    "stpde_jet_wgrad_nd": ([C.POINTER(LayerDesc), C.c_int] + [_VP] * 6 + [C.c_int, _VP], C.c_int),
+    "stpde_jet_tan0_reduce_nd": ([C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP], C.c_int),
     "stpde_jet_layer_fwd": ([C.POINTER(LayerDesc)] + [_VP] * 12, C.c_int),
     "stpde_jet_layer_bwd": ([C.POINTER(LayerDesc)] + [_VP] * 13, C.c_int),
     "stpde_jet_layer_bwd_to": ([C.POINTER(LayerDesc)] + [_VP] * 8, C.c_int),

@@ -37,6 +37,9 @@ struct WgradArgs {
   int det;             // dW addresses long accumulators (stpde_layer_desc.det, common.h: acc_add_f32)
   int bf16;            // != 0: contract with bf16-rounded operands (v_mfma_f32_16x16x32_bf16), fp32 accumulation
   int pk;              // packed-buffer flags (common.h: ld_blk): 1 = Q (the layer input's pre-activations), 4 = P (abar_out)
+  int ncoord;          // coordinate axes of the query (3; 1 or 2 for a query on a 1- / 2-d grid, stpde_jet_wgrad_nd): raw-input
+                       // column d >= ncoord is a latent channel, so the row sums of tangent-stream adjoint d -- the "unit vector
+                       // e_d" input of a skip connection -- are not added to it (exact fp32 and three-term split kernels)
   int xfold;           // fp32 hidden-group launches: the (k-group, k-slot) pairs 0 .. XT-1 also contract their abar blocks with
                        // raw-input tile 0 .. XT-1 (one extra 16x16 tile per wave, the XR fragment straight from memory), and all
                        // of them keep the row sums of the tangent-stream adjoints (the tangent "input" of a skip connection is the
@@ -225,7 +228,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_coop(WgradArgs a) {
           // tangent stream d sees the unit vector e_d: in the column-major image lane (g, row) holds features 4g .. 4g+3
           f32x4 v;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = (xt == 0 && 4 * g + r == d) ? 1.f : 0.f;
+          for (int r = 0; r < 4; ++r) v[r] = (xt == 0 && 4 * g + r == d && d < a.ncoord) ? 1.f : 0.f;
           put(&hl[buf][wv][1 + d][0], v, false);
         }
       }
@@ -341,7 +344,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_coop(WgradArgs a) {
   const bf16x4 one4 = to_bf4(f32x4{1.f, 1.f, 1.f, 1.f});
   const bool tanw = (XB || XS) && S1 == 3 && xslot == 0;
   const bf16x4 e0 = (tanw && c == 0) ? one4 : zero4;
-  const bf16x8 x8t = cat8((tanw && c == 1) ? one4 : zero4, (tanw && c == 2) ? one4 : zero4);
+  const bf16x8 x8t = cat8((tanw && c == 1 && a.ncoord > 1) ? one4 : zero4, (tanw && c == 2 && a.ncoord > 2) ? one4 : zero4);
   f32x4 xr = f32x4{0.f, 0.f, 0.f, 0.f};
   if constexpr (XF || XB || XS) {
 #pragma unroll
@@ -755,7 +758,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_coop(WgradArgs a) {
               float v = acct[d][mi];
               v += __shfl_xor(v, 16, 64);
               v += __shfl_xor(v, 32, 64);
-              if (g == 0) acc_add_f32(a.dW, (size_t)(16 * mt + c) * ldw + 16 * KT + d, v, a.det);
+              if (g == 0 && d < a.ncoord) acc_add_f32(a.dW, (size_t)(16 * mt + c) * ldw + 16 * KT + d, v, a.det);
             }
           }
         }
@@ -933,7 +936,7 @@ __global__ __launch_bounds__(256, (MCW * (KTT + XT) <= 8) ? 3 : ((MCW * (KTT + X
         float v = acct[d][mi];
         v += __shfl_xor(v, 16, 64);
         v += __shfl_xor(v, 32, 64);
-        if (g == 0) acc_add_f32(a.dW, (size_t)(16 * mt + c) * ldw + 16 * KTT + d, v, a.det);
+        if (g == 0 && d < a.ncoord) acc_add_f32(a.dW, (size_t)(16 * mt + c) * ldw + 16 * KTT + d, v, a.det);
       }
     }
   }
@@ -1101,7 +1104,7 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 3 : 2) void k_wgrad_quad(Wgrad
         float v = acct[d][mi];
         v += __shfl_xor(v, 16, 64);
         v += __shfl_xor(v, 32, 64);
-        if (g == 0) acc_add_f32(a.dW, (size_t)(16 * mi + c) * ldw + 16 * KTT + d, v, a.det);
+        if (g == 0 && d < a.ncoord) acc_add_f32(a.dW, (size_t)(16 * mi + c) * ldw + 16 * KTT + d, v, a.det);
       }
   }
 }

@@ -843,10 +843,10 @@ static int launch_reduce_nd_jet(const ReduceNdJetArgs& a, hipStream_t stream) {
   return stpde_check_launch("k_reduce_nd_jet");
 }
 
-extern "C" int stpde_lig_reduce_nd_jet_fwd(const stpde_jet_cfg* cfg, int S_mlp, int D, int P, int ntiles, int n_out,
-                                           const float* out_pre, const float* coef, float* jets, long ldp, void* stream) {
-  const char* who = "lig_reduce_nd_jet_fwd";
-  if (!cfg || !out_pre || !coef || !jets) {
+// the argument checks shared by stpde_lig_reduce_nd_jet_fwd and its adjoint (a, b, c: the three buffers)
+static int check_reduce_nd_jet(const char* who, const stpde_jet_cfg* cfg, int S_mlp, int D, int P, int ntiles, int n_out,
+                               long ldp, const void* a, const void* b, const void* c) {
+  if (!cfg || !a || !b || !c) {
     stpde_set_error("%s: null pointer", who);
     return STPDE_E_BADARG;
   }
@@ -875,8 +875,131 @@ extern "C" int stpde_lig_reduce_nd_jet_fwd(const stpde_jet_cfg* cfg, int S_mlp, 
     stpde_set_error("%s: S_mlp = %d outside 1..%d", who, S_mlp, 1 + cfg->S1 + cfg->S2);
     return STPDE_E_BADARG;
   }
+  return STPDE_OK;
+}
+
+extern "C" int stpde_lig_reduce_nd_jet_fwd(const stpde_jet_cfg* cfg, int S_mlp, int D, int P, int ntiles, int n_out,
+                                           const float* out_pre, const float* coef, float* jets, long ldp, void* stream) {
+  const int rc = check_reduce_nd_jet("lig_reduce_nd_jet_fwd", cfg, S_mlp, D, P, ntiles, n_out, ldp, out_pre, coef, jets);
+  if (rc) return rc;
   ReduceNdJetArgs a{*cfg, P, n_out, S_mlp, ldp, out_pre, coef, jets};
   return D == 1 ? launch_reduce_nd_jet<1>(a, (hipStream_t)stream) : launch_reduce_nd_jet<2>(a, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Adjoint of k_reduce_nd_jet (training through PDE residuals on 1- and 2-d grids): jets_bar [S][n_out][ldp] -> the adjoint of
+// the fc5 rows, over the forward's out_pre buffer.  Thread layout of k_reduce_bwd: one thread per (row tile, lane), lane (g, j)
+// holds output features 4g..4g+3 of row j and issues one 16-byte store per stream.  Row j of tile t belongs to point
+// p = t * (16 >> D) + (j >> D), corner j & (2^D - 1), mapped to the dim = 3 corner numbering as in the forward (first axis most
+// significant, the bits of the axes the grid does not have 0); the coefficient algebra is k_reduce_bwd's.  The rows
+// jets_bar[1 + k], k >= D, are NEVER read: the forward stores those outputs as the literal +0.0, so their cotangent is
+// dropped -- a NaN there reaches nothing -- and the adjoints of the tangent streams k >= D are written as +0.0.
+//
+// Addresses, bounded for every input value:
+//   grid      from ntiles alone: gid < ntiles * 64 (ntiles * 16 < 2^31, ceil(P / TP) <= ntiles <= that + 3: check_nd)
+//   abar_out  (tile * S_mlp + s) * 256 + lane * 4 + r, s < S_mlp, lane < 64, r < 4: ALL of [ntiles][S_mlp][256] is written --
+//             zeros for features >= n_out, padding rows (p >= P) and the tangent streams of the axes k >= D (the buffer held
+//             the forward's fc5 rows and the layer kernels read all of it)
+//   coef      p * 16 + i, i < 16, read only for p < P
+//   jets_bar  (s * n_out + ch) * ldp + p with s < S, ch = 4g + r < n_out, p < P <= ldp; nothing is read for p >= P
+// No index depends on a value read from memory: the pair indices come from the descriptor and are checked < D on the host.
+// ---------------------------------------------------------------------------------------------------------
+struct ReduceNdJetBwdArgs {
+  stpde_jet_cfg cfg;   // the streams of jets_bar
+  int P, ntiles, n_out;
+  int S_mlp;           // streams of dst (piecewise-linear activations carry no second-order streams)
+  long ldp;
+  const float* src;    // jets_bar [S][n_out][ldp]
+  const float* coef;   // [P][16]
+  float* dst;          // abar_out [ntiles][S_mlp][1][256]
+};
+
+template <int D>
+__global__ __launch_bounds__(256) void k_reduce_nd_jet_bwd(ReduceNdJetBwdArgs a) {
+  constexpr int TP = 16 >> D, NC = 1 << D;
+  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (size_t)a.ntiles * 64) return;
+  const int lane = gid & 63;
+  const size_t tile = gid >> 6;
+  const int g = lane >> 4, j = lane & 15;
+  const size_t p = tile * TP + (j >> D);
+  const int corner = j & (NC - 1);
+  const int S1 = a.cfg.S1, S2 = a.cfg.S2, S = 1 + S1 + S2;
+  float* base = a.dst + tile * (size_t)a.S_mlp * 256 + lane * 4;
+  f32x4 fbv[10];
+#pragma unroll
+  for (int s = 0; s < 10; ++s) fbv[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (p < (size_t)a.P && 4 * g < a.n_out) {
+    float cf[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f32x4 v = ld4(a.coef + p * 16 + 4 * i);
+      cf[4 * i] = v[0];
+      cf[4 * i + 1] = v[1];
+      cf[4 * i + 2] = v[2];
+      cf[4 * i + 3] = v[3];
+    }
+    const float* kap = cf + 12;
+    int c3 = 0;   // the corner in the dim = 3 numbering: first axis most significant, absent axes bit 0
+#pragma unroll
+    for (int k = 0; k < D; ++k) c3 |= corner_bit(corner, D, k) << (2 - k);
+    const CornerW c = corner_weights(cf, c3);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int ch = 4 * g + r;
+      if (ch >= a.n_out) continue;
+      float fb[10];
+#pragma unroll
+      for (int s = 0; s < 10; ++s) fb[s] = 0.f;
+      float yb[10];
+#pragma unroll
+      for (int s = 0; s < 10; ++s)
+        yb[s] = (s < S && !(s >= 1 + D && s < 4)) ? a.src[((size_t)s * a.n_out + ch) * a.ldp + p] : 0.f;
+      fb[0] = c.w * yb[0];
+      if (S1 == 3) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+          fb[0] += c.dw[d] * yb[1 + d];
+          fb[1 + d] = c.w * kap[d] * yb[1 + d];
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          if (k < S2) {
+            const int d = a.cfg.pair0[k], e = a.cfg.pair1[k];   // < D (checked on the host)
+            const float kd = sel3(d, kap[0], kap[1], kap[2]), ke = sel3(e, kap[0], kap[1], kap[2]);
+            const float dwd = sel3(d, c.dw[0], c.dw[1], c.dw[2]), dwe = sel3(e, c.dw[0], c.dw[1], c.dw[2]);
+            const float gg = yb[4 + k];
+            fb[0] += pair_ddw(c, d, e) * gg;
+            const float te = dwd * ke * gg;  // -> f_{1+e}
+            const float td = dwe * kd * gg;  // -> f_{1+d}
+#pragma unroll
+            for (int x = 0; x < D; ++x) fb[1 + x] += (e == x ? te : 0.f) + (d == x ? td : 0.f);
+            fb[4 + k] = c.w * kd * ke * gg;
+          }
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < 10; ++s) fbv[s][r] = fb[s];
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < 10; ++s)
+    if (s < a.S_mlp) st4(base + (size_t)s * 256, fbv[s]);
+}
+
+template <int D>
+static int launch_reduce_nd_jet_bwd(const ReduceNdJetBwdArgs& a, hipStream_t stream) {
+  const size_t n = (size_t)a.ntiles * 64;
+  STPDE_LAUNCH(k_reduce_nd_jet_bwd<D>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  return stpde_check_launch("k_reduce_nd_jet_bwd");
+}
+
+extern "C" int stpde_lig_reduce_nd_jet_bwd(const stpde_jet_cfg* cfg, int S_mlp, int D, int P, int ntiles, int n_out,
+                                           const float* jets_bar, long ldp, const float* coef, float* abar_out, void* stream) {
+  const int rc = check_reduce_nd_jet("lig_reduce_nd_jet_bwd", cfg, S_mlp, D, P, ntiles, n_out, ldp, jets_bar, coef, abar_out);
+  if (rc) return rc;
+  ReduceNdJetBwdArgs a{*cfg, P, ntiles, n_out, S_mlp, ldp, jets_bar, coef, abar_out};
+  return D == 1 ? launch_reduce_nd_jet_bwd<1>(a, (hipStream_t)stream) : launch_reduce_nd_jet_bwd<2>(a, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

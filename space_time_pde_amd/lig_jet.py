@@ -1,5 +1,5 @@
 """Host driver of the fused LIG + IM-NET jet path (dim = 3; value queries, and opt-in their training backward, also for
-dim = 1, 2, 4; opt-in forward-only jets also for dim = 1, 2) on libstpde_hip.
+dim = 1, 2, 4; opt-in jets, and opt-in their training backward, also for dim = 1, 2) on libstpde_hip.
 
 Computes y = query_local_implicit_grid(imnet, latent, pts) together with its first and selected second
 derivatives w.r.t. the query coordinates ("jets") in one forward pass of HIP kernels, and the gradients w.r.t.
@@ -58,6 +58,22 @@ def set_nd_jets(on):
     global nd_jets
     prev, nd_jets = nd_jets, bool(on)
     return prev
+
+
+# Opt-in: train THROUGH those derivatives -- gradients of a loss on the jets of a 1- or 2-d query (a PDE residual loss) w.r.t.
+# the latent grid and the IM-NET parameters in HIP (``set_nd_jet_backward`` / STPDE_ND_JET_BACKWARD=1, read once here).  Takes
+# effect only together with ``nd_jets``; independent of ``nd_backward``, which governs value-only queries.  Off, lig_jets
+# refuses a derivative request on such a grid that needs a gradient and PDELayer makes no request under grad mode, as before.
+nd_jet_backward = os.getenv("STPDE_ND_JET_BACKWARD", "0").strip().lower() not in ("", "0", "false", "no", "off")
+
+
+def set_nd_jet_backward(on):
+    """Switch the HIP training backward of dim = 1, 2 coordinate derivatives on or off (it needs ``nd_jets`` as well); returns
+    the previous setting."""
+    global nd_jet_backward
+    prev, nd_jet_backward = nd_jet_backward, bool(on)
+    return prev
+
 
 # Optional per-kernel timing (bench.py): set ``profile`` to a dict; every library call then records a pair of
 # events on the launch stream under its kernel name.  None = no overhead.
@@ -423,6 +439,7 @@ class JetCall:
     fc1_fused: bool         # bf16 mode: fused backward of the first hidden layer (STPDE_FC1_FUSED)
     nd_backward: bool       # dim = 1, 2, 4: the HIP training backward is allowed
     nd_jets: bool           # dim = 1, 2: coordinate derivatives in HIP are allowed (forward passes that need no gradient)
+    nd_jet_backward: bool   # dim = 1, 2: ... and so is their training backward (only together with ``nd_jets``)
     pipeline: bool          # driver: one library call per direction (dim = 3, no per-kernel profile), else kernel by kernel
     # ---- derived, computed once
     tail: bool              # the fused fc3 -> fc5 kernels serve this call's training stream set (_tail_applies)
@@ -472,6 +489,7 @@ class JetCall:
                    det_dlatent=bool(deterministic_dlatent), value_tiles=bool(value_tiles), tan0_rowsum=bool(tan0_rowsum),
                    wgrad_split=bool(wgrad_split), fused_tail=bool(fused_tail), fc1_fused=fc1_fused_enabled(),
                    nd_backward=bool(nd_backward), nd_jets=bool(nd_jets),
+                   nd_jet_backward=bool(nd_jets and nd_jet_backward),
                    pipeline=bool(use_pipeline and profile is None and dim == 3),
                    tail=tail, SP0=SP0, split0=bool(SP0 == 4 and tan0_rowsum), mult=mult)
 
@@ -789,9 +807,10 @@ def _forward_chunk(call, packs, packs16, latent, pts_c, jets, p0, need_grad=True
         with _timed("reduce_fwd"):
             check(L.stpde_lig_reduce_fwd(C.byref(call.cfg_out), S, Pc, plan.cout, ptr(bufs[5]), ptr(coef),
                                          C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2], st))
-    if nd and (nd_jet or not need_grad):    # no stash (lig_jets refuses a derivative request that needs a gradient)
+    if nd and not need_grad:    # no stash
         return None
-    # (dim = 1, 2, 4, ``nd_backward``: the backward needs the points again, for the cell ids -- stpde_lig_cell_nd)
+    # (dim = 1, 2, 4, ``nd_backward`` / ``nd_jet_backward``: the backward needs the points again, for the cell ids --
+    # stpde_lig_cell_nd; a derivative request keeps its coefficient records ``coef`` in the table's stash like dim = 3)
     s.update(pts_c=pts_c, p0=p0, Pc=Pc)
     return s
 
@@ -802,20 +821,39 @@ def _backward_chunk(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pba
 
     dim = 1, 2, 4 (``nd_backward``): stpde_lig_reduce_nd_bwd, the same S = 1 wgrad / dgrad sequence over the chunk's
     ``nd_tiles`` row tiles, then xbar_rows -> cell_nd -> cell_sort -> dlatent_reduce_nd.  d latent on these grids is ALWAYS
-    the deterministic per-node sum: ``deterministic_dlatent = False`` is ignored, there is no atomic variant."""
+    the deterministic per-node sum: ``deterministic_dlatent = False`` is ignored, there is no atomic variant.
+
+    dim = 1, 2 with derivative streams (``nd_jet_backward``): stpde_lig_reduce_nd_jet_bwd, then the sequence of dim = 3 with
+    ``call.S`` streams over the ``nd_tiles`` row tiles -- the weight gradients through stpde_jet_wgrad_nd /
+    stpde_jet_tan0_reduce_nd, which add the row sums of tangent adjoint k to raw-input column k for the axes k < dim only
+    (column k >= dim is a latent channel there) -- and the d latent calls of the value path on the value-stream adjoints."""
     if "ws" in saved:
         return _backward_chunk_c(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pbar, after_dlatent)
     plan, cfg, S = call.plan, call.cfg, call.S
     L, st = _lib.lib(), stream_ptr()
     Pc, p0, nd = saved["Pc"], saved["p0"], plan.dim != 3
+    nd_jet = nd and call.S_out > 1
     nt = _chunk_tiles(call, Pc)
+
+    def wgrad(d, SP, abar_out, in_pre, tanc0, dw, cw_):
+        """the weight gradient of one layer; a derivative request on a 1- / 2-d grid names its coordinate axes"""
+        if nd_jet:
+            return L.stpde_jet_wgrad_nd(C.byref(d), SP, ptr(abar_out), ptr(in_pre), ptr(X), ptr(tanc0), ptr(dw), ptr(cw_),
+                                        plan.dim, st)
+        return L.stpde_jet_wgrad(C.byref(d), SP, ptr(abar_out), ptr(in_pre), ptr(X), ptr(tanc0), ptr(dw), ptr(cw_), st)
+
     X, bufs, z0 = saved["X"], saved["bufs"], saved["z0"]
     coef, cell, cw = (saved.get(k) for k in ("coef", "cell", "cw"))
     dev = X.device
     pv = plan.pack_view
     SP0, split0, need_wgrad = call.SP0, call.split0, dw_flat is not None
     # adjoint of the fc5 output rows (overwrites the forward's out_pre buffer)
-    if nd:
+    if nd_jet:
+        with _timed("reduce_nd_jet_bwd"):
+            check(L.stpde_lig_reduce_nd_jet_bwd(C.byref(call.cfg_out), S, plan.dim, Pc, nt, plan.cout,
+                                                C.c_void_p(jets_bar.data_ptr() + 4 * p0), jets_bar.shape[2], ptr(coef),
+                                                ptr(bufs[5]), st))
+    elif nd:
         with _timed("reduce_nd_bwd"):
             check(L.stpde_lig_reduce_nd_bwd(plan.dim, Pc, nt, plan.cout, C.c_void_p(jets_bar.data_ptr() + 4 * p0),
                                             jets_bar.shape[2], ptr(saved["roww"]), ptr(bufs[5]), st))
@@ -854,8 +892,8 @@ def _backward_chunk(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pba
             continue
         if need_wgrad:
             with _timed("layer%d_wgrad" % l):
-                check(L.stpde_jet_wgrad(C.byref(dwg), S, ptr(abar[l]), ptr(bufs[l - 1]) if l > 1 else ptr(saved["z0"]),
-                                        ptr(X), ptr(pv(packs, 0, "tanc")), ptr(_dw_slice(call, dw_flat, l)), ptr(cw), st))
+                check(wgrad(dwg, S, abar[l], bufs[l - 1] if l > 1 else saved["z0"], pv(packs, 0, "tanc"),
+                            _dw_slice(call, dw_flat, l), cw))
         if call.tail and l >= 3:
             if l == 5:
                 arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
@@ -887,9 +925,12 @@ def _backward_chunk(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pba
             if split0:
                 d.cfg = call.cfg_val      # value stream x raw input (the S = 1 weight-gradient kernels)
                 check(L.stpde_jet_wgrad(C.byref(d), 1, ptr(abar0), None, ptr(X), None, ptr(dw0), None, st))
-                check(L.stpde_jet_tan0_reduce(nt, MT0, ptr(tan0), ptr(dw0), plan.dw_off[0][2], int(call.det), st))
+                if nd_jet:
+                    check(L.stpde_jet_tan0_reduce_nd(nt, MT0, ptr(tan0), ptr(dw0), plan.dw_off[0][2], int(call.det), plan.dim, st))
+                else:
+                    check(L.stpde_jet_tan0_reduce(nt, MT0, ptr(tan0), ptr(dw0), plan.dw_off[0][2], int(call.det), st))
             else:
-                check(L.stpde_jet_wgrad(C.byref(d), SP0, ptr(abar0), None, ptr(X), None, ptr(dw0), ptr(cw), st))
+                check(wgrad(d, SP0, abar0, None, None, dw0, cw))
     if dlatent is not None:
         xd = XbarDesc()
         xd.ntiles, xd.nlayers, xd.C = nt, 5, plan.cin
@@ -1255,6 +1296,19 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
     kernels in the request's stream set.  Returns (jets [1 + 3 + len(padded pairs), n_out, b*p], padded pairs) in the
     dim = 3 stream order; the streams d/dq_k, k >= dim, are +0.0.  Refused: ``combo``, a call that needs a gradient, bf16
     operands, dim = 4.
+
+    ... and with ``nd_jet_backward`` on top (``set_nd_jet_backward(True)`` / STPDE_ND_JET_BACKWARD=1; inert without
+    ``nd_jets``, independent of ``nd_backward``): such a call may need a gradient -- the jets are differentiable w.r.t. the
+    latent grid and the IM-NET parameters (a learnable swish beta included), which is what training with an equation loss on
+    a (t, x) or (x, y) model takes.  Backward: stpde_lig_reduce_nd_jet_bwd, the per-kernel layer / weight-gradient sequence
+    of dim = 3 in the call's stream set (weight gradients through stpde_jet_wgrad_nd / stpde_jet_tan0_reduce_nd: the tangent
+    streams of the axes k >= dim add nothing to the weight columns of latent channels), and the d latent calls of the value
+    path -- always the deterministic per-node sum.  A cotangent on the streams d/dq_k, k >= dim, is dropped, whatever it
+    holds.  Envelope: dim 1 or 2, in_features <= 32, fp32 or fp32x3 operands, pairs only, no point gradients (query_pts is
+    detached), the per-kernel driver, a single device.  Refused with NotImplementedError, never composed behind the caller's
+    back: ``combo``, bf16 operands, dim = 4, in_features > 32, and a call made while the point-sharded step's ``sync_hooks`` /
+    ``expect_two_phase`` are set (the one-call pipeline, ``use_pipeline``, stays dim = 3 only: such a call never takes it).
+    ``force_recompute``, a stash that does not fit and a second backward after ``retain_graph=True`` work as on dim = 3.
     """
     if not (latent_grid.is_cuda and query_pts.is_cuda):
         raise RuntimeError("the HIP jet path needs CUDA/HIP tensors (no CPU fallback)")
@@ -1306,13 +1360,19 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
         if any(not (0 <= a < dim and 0 <= b < dim) for a, b in pairs):
             raise ValueError("dim = %d: second-derivative pairs %r name an axis the grid does not have" % (dim, list(pairs)))
         if need_grad:
-            raise NotImplementedError("dim = %d coordinate derivatives run in HIP as forward passes only: call under "
-                                      "torch.no_grad() or without inputs / parameters that require grad" % dim)
+            if not call.nd_jet_backward:
+                raise NotImplementedError("dim = %d coordinate derivatives run in HIP as forward passes only: call under "
+                                          "torch.no_grad() or without inputs / parameters that require grad" % dim)
+            # the training backward of the derivative streams runs on one device (and kernel by kernel: ``JetCall.pipeline`` is
+            # dim = 3 only); the point-sharded step is refused when the call is made
+            if sync_hooks or expect_two_phase:
+                raise NotImplementedError("dim = %d: the training backward of coordinate derivatives does not serve the "
+                                          "point-sharded step (sync_hooks / expect_two_phase)" % dim)
     P = B * N
     if P == 0:   # empty query set: nothing to launch (the reference returns an empty [b, 0, o] tensor as well)
         return torch.zeros(call.S_out, plan.cout, 0, device=query_pts.device), call.pairs
     if dim != 3 and need_grad:
-        if not call.nd_backward:
+        if not (call.nd_jet_backward if wants_jets else call.nd_backward):
             raise NotImplementedError("dim = %d queries run in HIP as value-only forward passes: call under torch.no_grad() or "
                                       "without inputs / parameters that require grad" % dim)
         if plan.cin > ND_TRAIN_MAX_CHANNELS:

@@ -9,7 +9,8 @@ Value-only queries on 1-, 2- and 4-d grids (no jet request, nothing that needs a
 a corner sum of their own around the same IM-NET layer kernels (``_nd_value_eligible``).  With ``lig_jet.nd_backward``
 (opt-in) such a query also trains in HIP: gradients w.r.t. the latent grid and the IM-NET parameters (``_nd_train_eligible``).
 With ``lig_jet.nd_jets`` (opt-in) a PDE layer's derivative request on a 1- or 2-d grid that needs no gradient is answered by
-the HIP jet kernels too (``_nd_jet_eligible``).
+the HIP jet kernels too (``_nd_jet_eligible``); with ``lig_jet.nd_jet_backward`` on top (opt-in) so is one that trains
+through the residuals: gradients w.r.t. the latent grid and the IM-NET parameters (``_nd_jet_train_eligible``).
 Other decoders / dimensions / requests use the generic composed formulation.
 """
 import threading
@@ -116,8 +117,8 @@ def _nd_jet_eligible(model, latent_grid, query_pts, req=None):
     jet request for exactly these points, without a combined second-order stream and with pair indices < d; everything
     ``_nd_value_eligible`` asks for other than its request clause (ImNet decoder, CUDA fp32, nf a multiple of 16, out_features
     <= 16, d + in_features + 1 <= 36, every axis >= 2 nodes, fp32 or fp32x3 operands); and nothing that needs a gradient
-    (no_grad, or no point / latent grid / parameter requiring grad): the adjoint of the derivative streams on these grids is
-    not built.  d = 4, point gradients and training through residuals keep the composed formulation."""
+    (no_grad, or no point / latent grid / parameter requiring grad; a request that does is ``_nd_jet_train_eligible``'s).
+    d = 4 and point gradients keep the composed formulation."""
     if not lig_jet.nd_jets or req is None or req.x is not query_pts or req.combo:
         return False
     if not isinstance(model, ImNet) or model.dim not in lig_jet.ND_JET_DIMS:
@@ -125,6 +126,25 @@ def _nd_jet_eligible(model, latent_grid, query_pts, req=None):
     if any(not (0 <= a < model.dim and 0 <= b < model.dim) for a, b in req.pairs):
         return False
     return _nd_value_eligible(model, latent_grid, query_pts, None)     # (its gradient clause included)
+
+
+def _nd_jet_train_eligible(model, latent_grid, query_pts, req=None):
+    """A derivative request on a 1- or 2-d grid whose TRAINING BACKWARD the HIP path serves (opt-in on top of
+    ``lig_jet.nd_jets``: ``lig_jet.nd_jet_backward``, ``lig_jet.set_nd_jet_backward`` / STPDE_ND_JET_BACKWARD=1; off, this is
+    always False and such a request is composed, as before; ``lig_jet.nd_backward`` plays no part): grad mode on; everything
+    ``_nd_jet_eligible`` asks for other than its gradient clause (an active request for exactly these points, pairs with
+    indices < d, no combined stream, ImNet decoder itself -- not an nn.DataParallel --, CUDA fp32, nf a multiple of 16,
+    out_features <= 16, every axis >= 2 nodes, fp32 or fp32x3 operands -- not bf16); in_features <= 32 (the latent-adjoint
+    kernel k_xbar<XL> exists for XL = 1, 2); and the points themselves carry no gradient.  d = 4, the combined stream, bf16,
+    point gradients, wider latents and several devices keep the composed formulation."""
+    if not (lig_jet.nd_jets and lig_jet.nd_jet_backward) or not torch.is_grad_enabled() or query_pts.requires_grad:
+        return False
+    if isinstance(model, torch.nn.DataParallel) or getattr(model, "in_features", 0) > lig_jet.ND_TRAIN_MAX_CHANNELS:
+        return False
+    if req is None or not (req.first or req.pairs):     # (a request for the value alone trains as a value query: ``nd_backward``)
+        return False
+    with torch.no_grad():                   # = _nd_jet_eligible without its gradient clause
+        return _nd_jet_eligible(model, latent_grid, query_pts, req)
 
 
 def _xmin_is_zero(xmin, xmax=None, shape3=None):
@@ -211,7 +231,8 @@ def query_local_implicit_grid(model, latent_grid, query_pts, xmin, xmax):
             jets, _ = lig_jet.lig_jets(model, latent_grid, query_pts, xmin, xmax, False, ())
             stats["hip_value_calls"] += 1
             return jets[0].t().reshape(query_pts.shape[0], query_pts.shape[1], jets.shape[1])
-    if _nd_jet_eligible(model, latent_grid, query_pts, req) and _xmin_is_zero(xmin, xmax, tuple(latent_grid.shape[1:-1])):
+    if (_nd_jet_eligible(model, latent_grid, query_pts, req) or _nd_jet_train_eligible(model, latent_grid, query_pts, req)) \
+            and _xmin_is_zero(xmin, xmax, tuple(latent_grid.shape[1:-1])):
         jets, pairs = lig_jet.lig_jets(model, latent_grid, query_pts, xmin, xmax, req.first, req.pairs)
         stats["hip_jet_calls"] += 1
         y = jets[0].t().reshape(query_pts.shape[0], query_pts.shape[1], jets.shape[1])

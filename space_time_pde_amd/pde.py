@@ -369,8 +369,9 @@ class PDELayer(object):
         if nd:
             # 1- and 2-d problems (opt-in, ``lig_jet.nd_jets``): the HIP jets there serve forward passes that need no
             # gradient, so a request is made with grad mode off only -- with it on the forward would be evaluated for the
-            # request, find it unserved and be evaluated again by the reverse sweeps
-            if not _lig.lig_jet.nd_jets or torch.is_grad_enabled():
+            # request, find it unserved and be evaluated again by the reverse sweeps -- unless their training backward is
+            # switched on as well (``lig_jet.nd_jet_backward``)
+            if not (_lig.lig_jet.nd_jets and (not torch.is_grad_enabled() or _lig.lig_jet.nd_jet_backward)):
                 return None
         elif self.n_in != 3:
             return None

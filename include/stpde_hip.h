@@ -70,13 +70,21 @@ int stpde_last_error(char* buf, unsigned long n);
  * test forces other values to reach their multi-block and ragged-tail paths on volumes it can afford.  value 0 = the library's
  * own choice (the default of every key).  Keys: "conv3_lds_off" (1: the 3x3x3 LDS-tile kernel is not used),
  * "conv3_lds_minblk" (minimum number of blocks for it), "conv3_lds_gx", "conv_wgrad_lds_gx", "conv1_wgrad_lds_gx" (grid sizes).
+ * "wgrad_fp32_swap": loop body of the exact-fp32 first-hidden-layer weight-gradient kernel (k_wgrad_coop, MODE 1, at most five
+ * streams, every stream in the adjoint buffer): 0 = the library's own choice (the phase-swapped loop), 1 = the phase-swapped
+ * loop, 2 = the lock-step loop.  The two loops differ for EVERY wave, not only in the phase order of waves 4 .. 7: in the
+ * phase-swapped loop all eight waves fetch their next adjoint operand set in the row-major image with dword loads spread over
+ * the MFMAs (no transposes through the LDS patch), and waves 4 .. 7 build their ring slot before their MFMAs instead of behind
+ * them; the lock-step loop restores the old load form for all waves.  The results are the same bits either way (A/B timing,
+ * tests/test_gpu_wgrad_fp32_phase_swap.py).
  * Returns the previous value, -1 for an unknown key.  Process-wide, thread-safe. */
 #define STPDE_TUNE_CONV3_LDS_OFF 0
 #define STPDE_TUNE_CONV3_LDS_MINBLK 1
 #define STPDE_TUNE_CONV3_LDS_GX 2
 #define STPDE_TUNE_CONV_WGRAD_LDS_GX 3
 #define STPDE_TUNE_CONV1_WGRAD_LDS_GX 4
-#define STPDE_TUNE_COUNT 5
+#define STPDE_TUNE_WGRAD_FP32_SWAP 5
+#define STPDE_TUNE_COUNT 6
 int stpde_tune(const char* name, int value);
 /* Dispatch trace (test / debugging facility; nothing in the reference corresponds to it): while enabled, every kernel
  * launch records which template instantiation it dispatched ("<kernel expression> @ <launcher with template

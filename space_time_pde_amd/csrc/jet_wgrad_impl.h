@@ -45,6 +45,10 @@ struct WgradArgs {
                        // of them keep the row sums of the tangent-stream adjoints (the tangent "input" of a skip connection is the
                        // unit vector e_d): no separate launch for the three raw-input k-tiles, which re-read and re-transposed every
                        // abar block of the layer for 3 / 35 of the MFMA work (9.3 + 5.9 ms per step for layers 1 and 2)
+  int swap;            // exact fp32, first hidden layer: the SWAP32 loop of k_wgrad_coop instead of the lock-step loop -- ALL waves
+                       // load the next adjoint set row-major between their MFMAs (no patch transposes), and waves 4 .. 7 run the
+                       // two phases of an iteration in the other order (set by the launcher from stpde_tune "wgrad_fp32_swap" when
+                       // SP == S; same bits either way)
   stpde_jet_cfg cfg;
 };
 
@@ -418,6 +422,57 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_coop(WgradArgs a) {
       __builtin_amdgcn_sched_barrier(0);
     }
   };
+  // exact fp32, hidden k-groups (XF): the folded raw-input product and the tangent row sums of the current row tile -- part of
+  // its MFMA phase (branch-free: without xfold the pointer is this launch's own X anyway and the results are simply not written)
+  auto xf_fold = [&]() {
+    if constexpr (XF) {
+      const f32x4 xrr = x_rowmajor(xr);
+#pragma unroll
+      for (int mi = 0; mi < MCW; ++mi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) accx[mi] = mfma4(pa[0][mi][r], xrr[r], accx[mi]);
+      if constexpr (S1 == 3) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+#pragma unroll
+          for (int mi = 0; mi < MCW; ++mi)
+            acct[d][mi] += (pa[1 + d][mi][0] + pa[1 + d][mi][1]) + (pa[1 + d][mi][2] + pa[1 + d][mi][3]);
+      }
+    }
+  };
+  // Exact fp32, hidden k-groups (round 5): the MFMAs of a row tile out of ring buffer `rb`.  Read stream-innermost the compiler
+  // emitted `2 x ds_read_b128 ; s_waitcnt lgkmcnt(1) ; 4 MFMAs ; s_waitcnt lgkmcnt(0) ; ...` -- 19 waits to zero per iteration,
+  // each with at most one 32-cycle MFMA in flight to cover an LDS round trip (tools/micro/isa_waits.py).  Here the block of
+  // (k-slot, stream) n + 1 is requested before the MCW * 4 MFMAs of block n (256 cycles of matrix work per block), the order of
+  // ring reads and MFMAs pinned; everything else may move across the pins.  (The sums of a dW element are accumulated stream by
+  // stream instead of k-step by k-step: same terms, another fp32 rounding order.)
+  // `side(n)` is called in front of the MFMAs of block n = ki * S + st (loads sprinkled through the matrix phase); `pin_c` says
+  // what may NOT cross the pins around a block's MFMAs.
+  constexpr int PIN_MFMA_DSR = 0x2 | 0x4 | 0x10 | 0x20 | 0x40 | 0x200;  // VALU, SALU, VMEM and DS writes may cross; MFMA / DS reads not
+  constexpr int PIN_MFMA_DSR_VMEM = 0x2 | 0x4 | 0x200;                  // ... and vector-memory instructions stay where they are written
+  auto ring_mma32 = [&](int rb, auto pin_c, auto&& side) {
+    constexpr int PIN = decltype(pin_c)::value;
+    f32x4 Hc = get(&hl[rb][ks * KC][0][0]);
+#pragma unroll
+    for (int ki = 0; ki < KC; ++ki) {
+      const int q = ks * KC + ki;
+#pragma unroll
+      for (int st = 0; st < S; ++st) {
+        f32x4 Hn = Hc;
+        if (st + 1 < S) Hn = get(&hl[rb][q][st + 1][0]);
+        else if (ki + 1 < KC) Hn = get(&hl[rb][q + 1][0][0]);
+        __builtin_amdgcn_sched_barrier(PIN);
+        side(ki * S + st);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int mi = 0; mi < MCW; ++mi) acc[mi][ki] = mfma4(pa[st][mi][r], Hc[r], acc[mi][ki]);
+        __builtin_amdgcn_sched_barrier(PIN);
+        Hc = Hn;
+      }
+    }
+  };
+  auto no_side = [](int) {};
   if (tile < a.ntiles) {
     f32x4 raw[S][MCW];
     produce(tile, 0);
@@ -522,6 +577,78 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_coop(WgradArgs a) {
       }
     }
   }
+  // The same swap for the exact-fp32 kernel of the first hidden layer (S <= 5; WgradArgs.swap, same bits either way).  The bf16
+  // form above does not fit here: fp32 blocks in flight, their transposed copy in a staging set and the current operand set are
+  // 3 x S * MCW * 4 = 120 registers next to 64 accumulators.  And the swap alone buys little: per row tile a wave spends ~10,200
+  // cycles in its MFMAs and ~6,200 in the preparation, 3,200 of them in the S * MCW dependent patch round trips that transpose
+  // its adjoint blocks; the two waves of a SIMD share the matrix pipe evenly, so the wave that starts its MFMAs first finishes
+  // them only ~1,400 cycles before its partner and its long preparation stays exposed (22.6 -> 22.1 ms per 2^18 points with
+  // the swapped half alone on this loop form; s_setprio on either half made it slower).  So here EVERY wave loads the next
+  // tile's adjoint fragments already in the row-major image -- lane (g, c): rows 4g .. 4g+3 of feature c = four dword loads, 16
+  // bytes apart, per block -- straight into the set that becomes the operand set behind the MFMAs: no raw set, no patch round
+  // trip, two sets instead of three.  The S * MCW * 4 = 40 dword loads are written one in front of each block of 8 MFMAs
+  // (requested in one burst they stall the wave at the address queue in front of its matrix phase: that form measured neutral
+  // in round 6).  What is left of the preparation is the ring slot; waves 4 .. 7 build it BEFORE their MFMAs, waves 0 .. 3
+  // behind them.  22.6 -> 21.1 ms; the row-major loads without the swap 22.5 ms.  Every wave keeps its accumulators, its tile
+  // order and its MFMA order (xf_fold, then ring_mma32), so the results are the bits of the lock-step loop below.
+  constexpr bool SWAP32 = !BF && SPL == 1 && PKM == 0 && MODE == 1 && !HASX && NBUF == 2 && S <= 5 && STPDE_WG_RPIPE;
+  if constexpr (SWAP32) {
+    if (a.swap) {
+      const bool late = wv >= NW / 2;                          // this wave prepares the next tile BEFORE its MFMAs
+      const int rmo = (c >> 2) * 64 + 16 * g + (c & 3);      // element (feature c, row 4g) of a column-major fragment image
+      const int mtc0 = mt0 < MT ? mt0 : MT - 1, mtc1 = mt0 + 1 < MT ? mt0 + 1 : MT - 1;
+      f32x4 pn[S][MCW];
+      // the z0 block -- the one HBM load of the produce stage -- is requested in front of the MFMAs that precede its use: by a
+      // late wave for the tile after next
+      f32x4 z0n = f32x4{0.f, 0.f, 0.f, 0.f}, xrn = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (late && tile < a.ntiles)
+        z0n = ld4(a.Q + ((size_t)(tile + stride < a.ntiles ? tile + stride : tile) * KT + kq0 + wv) * 256 + lo);
+      auto prep = [&](int t) {                                // ring slot of tile t (everything but z0 comes from L2)
+        if (STPDE_ABLATE_W != 3) {
+          f32x4 preq[S];
+          float cqq[6];
+          load_q(t, preq, cqq);
+          preq[0] = z0n;
+          finish_q(preq, cqq, buf ^ 1);
+        }
+      };
+      for (; tile < a.ntiles; tile += stride) {
+        const int next = tile + stride;
+        const int nx = next < a.ntiles ? next : tile;           // branch-free tail, as below
+        const int nn = nx + stride < a.ntiles ? nx + stride : nx;
+        if (late) prep(nx);
+        __builtin_amdgcn_sched_barrier(0);
+        z0n = ld4(a.Q + ((size_t)(late ? nn : nx) * KT + kq0 + wv) * 256 + lo);
+        xrn = ld4(a.X + ((size_t)nx * XT + xsel) * 256 + lo);
+        const float* pb = a.P + (size_t)nx * S * MT * 256 + rmo;      // (a.swap: SP == S, every stream is in the buffer)
+        __builtin_amdgcn_sched_barrier(0);
+        xf_fold();
+        ring_mma32(buf, std::integral_constant<int, PIN_MFMA_DSR_VMEM>{}, [&](int n) {
+          // the S * MCW * 4 dwords of the next operand set over the KC * S ring blocks of the matrix phase (KC = 8: one each);
+          // dword e: block (st, mi) = e / 4, row 4g + e % 4
+          constexpr int DPB = (MCW * 4 + KC - 1) / KC;
+          if (STPDE_ABLATE_W != 2) {
+#pragma unroll
+            for (int e = n * DPB; e < (n + 1) * DPB && e < S * MCW * 4; ++e) {
+              const int st = e / (4 * MCW), mi = (e / 4) % MCW, r = e % 4;
+              pn[st][mi][r] = pb[((size_t)st * MT + (mi ? mtc1 : mtc0)) * 256 + 4 * r];
+            }
+          }
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        if (!late) prep(nx);
+        if (STPDE_ABLATE_W != 2) {
+#pragma unroll
+          for (int st = 0; st < S; ++st)
+#pragma unroll
+            for (int mi = 0; mi < MCW; ++mi) pa[st][mi] = pn[st][mi];
+        }
+        xr = xrn;
+        if (STPDE_ABLATE_W != 5) __syncthreads();
+        buf ^= 1;
+      }
+    }
+  }
   for (; tile < a.ntiles; tile += stride) {
     const int next = tile + stride;
     const int nx = next < a.ntiles ? next : tile;   // branch-free tail: the last iteration re-produces its own tile
@@ -553,20 +680,8 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_coop(WgradArgs a) {
       xs_mma();
     }
     if constexpr (XF) {
-      // branch-free: without xfold the pointer is this launch's own XR anyway and the results are simply not written
       xrn = ld4(a.X + ((size_t)nx * XT + xsel) * 256 + lo);
-      const f32x4 xrr = x_rowmajor(xr);
-#pragma unroll
-      for (int mi = 0; mi < MCW; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) accx[mi] = mfma4(pa[0][mi][r], xrr[r], accx[mi]);
-      if constexpr (S1 == 3) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d)
-#pragma unroll
-          for (int mi = 0; mi < MCW; ++mi)
-            acct[d][mi] += (pa[1 + d][mi][0] + pa[1 + d][mi][1]) + (pa[1 + d][mi][2] + pa[1 + d][mi][3]);
-      }
+      xf_fold();
     }
     if constexpr (SPLP && !HASX && KC % 2 == 0) {
       // split mode, hidden k-tiles: two k-tiles at a time and the six partial products outermost, so that consecutive
@@ -597,32 +712,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_coop(WgradArgs a) {
     } else if constexpr (BF && SPL == 1 && !HASX && STPDE_ABLATE_W == 0) {
       ring_mma(buf);
     } else if constexpr (!BF && !HASX && STPDE_WG_RPIPE) {
-      // Exact fp32, hidden k-groups (round 5).  The loop below reads the S ring blocks of a k-slot and issues its MCW * 4 * S
-      // MFMAs stream-innermost, and the compiler emitted `2 x ds_read_b128 ; s_waitcnt lgkmcnt(1) ; 4 MFMAs ; s_waitcnt
-      // lgkmcnt(0) ; ...` -- 19 waits to zero per iteration, each with at most one 32-cycle MFMA in flight to cover an LDS round
-      // trip (tools/micro/isa_waits.py; both waves of a SIMD are in this phase at the same time).  Here the block of
-      // (k-slot, stream) n + 1 is requested before the MCW * 4 MFMAs of block n (256 cycles of matrix work per block), the
-      // order of ring reads and MFMAs pinned; everything else may move across the pins.  (The sums of a dW element are
-      // accumulated stream by stream instead of k-step by k-step: same terms, another fp32 rounding order.)
-      constexpr int PIN = 0x2 | 0x4 | 0x10 | 0x20 | 0x40 | 0x200;      // VALU, SALU, VMEM and DS writes may cross; MFMA / DS reads not
-      f32x4 Hc = get(&hl[buf][ks * KC][0][0]);
-#pragma unroll
-      for (int ki = 0; ki < KC; ++ki) {
-        const int q = ks * KC + ki;
-#pragma unroll
-        for (int st = 0; st < S; ++st) {
-          f32x4 Hn = Hc;
-          if (st + 1 < S) Hn = get(&hl[buf][q][st + 1][0]);
-          else if (ki + 1 < KC) Hn = get(&hl[buf][q + 1][0][0]);
-          __builtin_amdgcn_sched_barrier(PIN);
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int mi = 0; mi < MCW; ++mi) acc[mi][ki] = mfma4(pa[st][mi][r], Hc[r], acc[mi][ki]);
-          __builtin_amdgcn_sched_barrier(PIN);
-          Hc = Hn;
-        }
-      }
+      ring_mma32(buf, std::integral_constant<int, PIN_MFMA_DSR>{}, no_side);
     } else {
 #pragma unroll
     for (int ki = 0; ki < KC; ++ki) {
@@ -1299,6 +1389,9 @@ static int launch_wgrad_kc(const WgradArgs& a0, hipStream_t stream) {
   constexpr bool SPLIT_OK = KC >= 4 && S1 + S2 <= 4;
   const int bfm = (a.bf16 == 3 && !SPLIT_OK) ? 0 : a.bf16;
   const bool xfold = (!bfm || (bfm == 1 && KC >= 4) || (bfm == 3 && KC >= 4 && STPDE_X3_XFOLD)) && a.KT > 0 && a.KT % 8 == 0 && nhid * kslots >= XT && a.X;
+  // phase-swapped order of waves 4 .. 7 (SWAP32 in k_wgrad_coop): its adjoint loads are unconditional, so every stream has to
+  // be in the buffer
+  a.swap = (stpde_tune_get(STPDE_TUNE_WGRAD_FP32_SWAP) != 2 && a.SP == 1 + S1 + S2) ? 1 : 0;
   for (int part = 0; part < 2; ++part) {
     a.kz0 = part == 0 ? 0 : nhid;
     a.gz = part == 0 ? nhid : ngr - nhid;

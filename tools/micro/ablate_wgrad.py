@@ -1,5 +1,6 @@
 """Timing-only ablations of the first-hidden-layer weight-gradient kernel in the bf16-pipe modes (S = (3,1) softplus,
-nf = 32): private builds of jet_wgrad.hip + jet_wgrad_s31.hip with -DSTPDE_ABLATE_W=n (see jet_wgrad_impl.h).
+nf = 32): private builds of jet_wgrad.hip + jet_wgrad_s31.hip with -DSTPDE_ABLATE_W=n (see jet_wgrad_impl.h).  The exact-fp32
+kernel is timed in both loop orders of its waves 4 .. 7 (lock step / phase-swapped: profiles/wgrad_fp32_phase_swap.txt).
 
     python tools/micro/ablate_wgrad.py build      # here (no GPU)
     python tools/micro/ablate_wgrad.py run        # on the GPU box
@@ -14,6 +15,7 @@ sys.path.insert(0, ROOT)
 CSRC = os.path.join(ROOT, "space_time_pde_amd", "csrc")
 OUT = os.path.join(ROOT, "tools", "micro", "_abl")
 VARIANTS = [int(v) for v in os.environ.get("ABLW_VARIANTS", "0,1,2,3,4,5").split(",")]
+MODES = os.environ.get("ABLW_MODES", "fp32x3,bf16,fp32").split(",")      # ABLW_MODES=fp32: the exact-fp32 lines only
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics"]
 
 
@@ -69,6 +71,8 @@ def run(tags=None):
     names = {0: "baseline", 1: "one partial product instead of six", 2: "abar transposed / split for the first tile only",
              3: "no produce stage in the loop", 4: "consumer operands not read from LDS", 5: "no barrier in the loop"}
     for mode, tag in ((3, "fp32x3"), (1, "bf16"), (0, "fp32")):
+        if tag not in MODES:
+            continue
         for n in (tags or VARIANTS):
             so = os.path.join(OUT, "libablw_%s.so" % n)
             if not os.path.exists(so) or (not tags and mode != 3 and n not in (0, 2, 3, 5)):
@@ -83,15 +87,20 @@ def run(tags=None):
             def fn():
                 return L.stpde_jet_wgrad(C.byref(d), S, p(abar1), p(z0), p(XR), p(pv(packs, 0, "tanc")), p(dw), p(cw), st)
 
-            assert fn() == 0
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(3):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            print("%-7s %-50s %7.3f ms" % (tag, names.get(n, n), e0.elapsed_time(e1) / 3))
+            # exact fp32: both loop orders of waves 4 .. 7 (stpde_tune "wgrad_fp32_swap": 2 = lock step, 1 = phase-swapped);
+            # every private build carries its own copy of the switch
+            for order, oname in (((2, "lock step"), (1, "swapped")) if mode == 0 else ((0, ""),)):
+                L.stpde_tune(b"wgrad_fp32_swap", order)
+                assert fn() == 0
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(3):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                label = names.get(int(n), n) if str(n).isdigit() else n          # (tags given on the command line are strings)
+                print("%-7s %-9s %-50s %7.3f ms" % (tag, oname, label, e0.elapsed_time(e1) / 3))
 
 
 if __name__ == "__main__":

@@ -15,6 +15,12 @@ Two evaluation strategies:
   grid query it answers with forward-mode jets computed by the CDNA4 kernels, and the residual is plain
   elementwise algebra on them.  If the forward method is anything else (or post-processes the query result) the
   generic strategy is used, exactly like the reference.
+
+Coefficients (an extension of the reference surface): ``PDELayer(in_vars, out_vars, param_vars='nu')`` declares symbols whose
+values are tensors handed over with ``update_parameters`` -- one value for all points or one per batch element, optionally
+requiring grad (inverse problems, mixed-regime batches).  Both torch strategies take them.  The HIP residual evaluator does
+not: with the HIP jets the residual algebra of such a layer is evaluated by the lambdified torch functions (counted and
+reported once as ``residual_torch_fallbacks``).
 """
 import ctypes as C
 
@@ -195,14 +201,19 @@ class _ResidualHip(torch.autograd.Function):
 class PDELayer(object):
     """PDE Layer for querying values and computing PDE residues."""
 
-    def __init__(self, in_vars, out_vars):
-        """in_vars / out_vars: strings of variable names, e.g. 'x, y, t' and 'u, v, p'."""
+    def __init__(self, in_vars, out_vars, param_vars=''):
+        """in_vars / out_vars: strings of variable names, e.g. 'x, y, t' and 'u, v, p'; param_vars: names of coefficient
+        symbols (e.g. 'nu' or 'Ra, Pr') whose values ``update_parameters`` sets."""
         self.in_vars = sympy.symbols(in_vars)
         self.out_vars = sympy.symbols(out_vars)
+        self.param_vars = sympy.symbols(param_vars) if param_vars.strip() else ()
         if not isinstance(self.in_vars, tuple):
             self.in_vars = (self.in_vars,)
         if not isinstance(self.out_vars, tuple):
             self.out_vars = (self.out_vars,)
+        if not isinstance(self.param_vars, tuple):
+            self.param_vars = (self.param_vars,)
+        self.params = {}     # {name: tensor} set by update_parameters
         self.n_in = len(self.in_vars)
         self.n_out = len(self.out_vars)
         self.all_vars = list(self.in_vars) + list(self.out_vars)
@@ -217,7 +228,7 @@ class PDELayer(object):
     def add_equation(self, eqn_str, eqn_name='', subs_dict=None):
         """Add the residue expression of one equation; ``dif(y,x)`` denotes dy/dx (reference :37-86).
 
-        Raises ValueError when the expression uses symbols outside in_vars/out_vars.
+        Raises ValueError when the expression uses symbols outside in_vars/out_vars/param_vars.
         """
         if not eqn_name:
             # the reference formats 'eqn_{i}' with a positional argument and therefore raises KeyError here
@@ -227,12 +238,12 @@ class PDELayer(object):
         if subs_dict:
             for key, val in subs_dict.items():   # sequential substitution, as the reference
                 expr = expr.subs(key, val)
-        valid_var = expr.free_symbols <= (set(self.in_vars) | set(self.out_vars))
+        valid_var = expr.free_symbols <= (set(self.in_vars) | set(self.out_vars) | set(self.param_vars))
         if not valid_var:
             raise ValueError('Variables in the eqn_str ({}) does not match that of '
-                             'in_vars ({}) and out_vars ({})'.format(expr.free_symbols, set(self.in_vars),
-                                                                     set(self.out_vars)))
-        fn = sympy.lambdify(self.all_vars, expr, [{'dif': torch_diff}, _TORCH_FUNCS])
+                             'in_vars ({}), out_vars ({}) and param_vars ({})'.format(
+                                 expr.free_symbols, set(self.in_vars), set(self.out_vars), set(self.param_vars)))
+        fn = sympy.lambdify(self.all_vars + list(self.param_vars), expr, [{'dif': torch_diff}, _TORCH_FUNCS])
         self.eqns_raw.update({eqn_name: eqn_str})
         self.eqns_fn.update({eqn_name: fn})
         self.eqns_jet.update({eqn_name: self._compile_jet(expr)})
@@ -293,7 +304,7 @@ class PDELayer(object):
                 atoms = [(k, v) for k, v in prog.syms.items() if len(k[1]) < 2] + \
                         [((c, ("L",)), v) for c, v in lam.items()]
                 atoms.sort(key=lambda a: (a[0][0], len(a[0][1]), str(a[0][1])))
-                fn = sympy.lambdify(list(self.in_vars) + [a[1] for a in atoms], e, [_TORCH_FUNCS])
+                fn = sympy.lambdify(list(self.in_vars) + list(self.param_vars) + [a[1] for a in atoms], e, [_TORCH_FUNCS])
                 new[name] = _JetProgram(fn, [a[0] for a in atoms], e, {a[0]: a[1] for a in atoms})
             self._combo = dict(alpha=alpha, progs=new)
         except Exception as exc:   # any sympy corner case -> one stream per pair (never wrong, only slower)
@@ -337,7 +348,7 @@ class PDELayer(object):
             if e.atoms(AppliedUndef):
                 return None
             atoms.sort(key=lambda a: (a[0][0], len(a[0][1]), a[0][1]))
-            fn = sympy.lambdify(list(self.in_vars) + [a[1] for a in atoms], e, [_TORCH_FUNCS])
+            fn = sympy.lambdify(list(self.in_vars) + list(self.param_vars) + [a[1] for a in atoms], e, [_TORCH_FUNCS])
             return _JetProgram(fn, [a[0] for a in atoms], e, {a[0]: a[1] for a in atoms})
         except Exception as exc:  # any sympy corner case -> generic strategy (never wrong, only slower)
             _note_fallback("jet_compile_errors", "equation %s could not be expanded into jets (%r): reverse-sweep strategy"
@@ -348,6 +359,37 @@ class PDELayer(object):
     def update_forward_method(self, forward_method):
         """forward_method: y = forward_method(x), x (..., n_in) -> y (..., n_out)."""
         self.forward_method = forward_method
+
+    def update_parameters(self, values):
+        """values: {name: tensor} for names of ``param_vars``; fp32 of shape [], [1] (one value for all points) or [B] (one
+        per batch element of the query points [B, N, n_in]).  A value may require grad: the residuals are differentiable
+        w.r.t. it on every strategy.  The tensors are kept, not copied: an in-place update is seen by the next call."""
+        names = {s.name for s in self.param_vars}
+        for name, t in values.items():
+            if name not in names:
+                raise ValueError('{} is not one of the declared param_vars ({})'.format(name, sorted(names)))
+            if not (torch.is_tensor(t) and t.dtype == torch.float32):
+                raise ValueError('parameter {} must be a float32 tensor'.format(name))
+            if t.dim() > 1:
+                raise ValueError('parameter {} has shape {}: expected [], [1] or [B]'.format(name, tuple(t.shape)))
+        self.params.update(values)
+
+    def _param_values(self, x):
+        """The coefficient tensors in the order of param_vars, checked against the batch size of the query points x."""
+        vals = []
+        for s in self.param_vars:
+            if s.name not in self.params:
+                raise RuntimeError('parameter {} has not been set. Run update_parameters first.'.format(s.name))
+            t = self.params[s.name]
+            if t.numel() != 1 and t.shape[0] != x.shape[0]:
+                raise ValueError('parameter {} has {} values, the query points have batch size {}'.format(
+                    s.name, t.shape[0], x.shape[0]))
+            vals.append(t)
+        return vals
+
+    def _param_broadcast(self, x):
+        """[B, 1, ...] / [1, 1, ...] views of the coefficients, broadcastable against the columns of x."""
+        return [t.reshape((-1,) + (1,) * (x.dim() - 1)) for t in self._param_values(x)]
 
     def eval(self, x):
         """Evaluate the output values using forward_method (reference :97-113)."""
@@ -408,7 +450,7 @@ class PDELayer(object):
         if jets.is_cuda:
             _note_fallback("residual_torch_fallbacks", "an equation uses an expression the HIP residual evaluator does not "
                            "implement: residuals evaluated with the lambdified torch functions")
-        cols = [x[..., i:i + 1] for i in range(self.n_in)]
+        cols = [x[..., i:i + 1] for i in range(self.n_in)] + [t.to(jets.device) for t in self._param_broadcast(x)]
         cache = {}
 
         def atom(key):
@@ -423,6 +465,8 @@ class PDELayer(object):
         torch kernels; None when an equation uses something the device evaluator does not implement."""
         if not (jets.is_cuda and jets.dtype == torch.float32 and all(p.expr is not None for p in progs.values())):
             return None
+        if self.param_vars:
+            return None     # coefficients in tensors: the device evaluator reads constants only
         key = (tuple(sorted((str(k), v) for k, v in stream_of.items())), str(jets.device))
         ent = self._res_progs.get(key, False)
         if ent is False:
@@ -465,6 +509,7 @@ class PDELayer(object):
         outputs = [y[..., i:i + 1] for i in range(y.shape[-1])]
         inputs_outputs = inputs + outputs
         residues = {}
+        inputs_outputs = inputs_outputs + self._param_broadcast(x)
         for key, fn in self.eqns_fn.items():
             residues.update({key: fn(*inputs_outputs)})
         return y, residues

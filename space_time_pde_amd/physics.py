@@ -8,7 +8,13 @@ nu_t = 1/t_crop, nu_x = 1/x_crop, nu_z = 1/z_crop, P = (Ra Pr)^-1/2, R = (Ra/Pr)
     continuity     : nu_x u_x + nu_z w_z                                   (optional)
 Input variables are named 't, x, z' and are POSITIONAL (column 0, 1, 2 of the query points) exactly as in the
 reference (quirk a-Q4: the data's axis order is (t, z, x), so the symbol x differentiates the data's z axis).
+
+``prandtl`` / ``rayleigh`` may be tensors (fp32, shape [], [1] or [B]: one regime per batch element; they may require grad):
+the layer then declares the coefficients ``Ra, Pr``, writes P and R in terms of them and hands the values to
+``PDELayer.update_parameters``.  With numbers the equation strings are what they always were.
 """
+import torch
+
 from .pde import PDELayer
 
 _OUT = ('p', 'b', 'u', 'w')
@@ -28,8 +34,12 @@ def get_rb2_pde_layer(mean=None, std=None, t_crop=2., z_crop=1., x_crop=2., pran
     mean/std: per-channel (p, b, u, w) normalisation constants or None; when given, every channel v is replaced by
     v*std+mean inside and outside ``dif`` (change of variables, reference :38-56).
     """
-    P = (rayleigh * prandtl) ** (-1 / 2)
-    R = (rayleigh / prandtl) ** (-1 / 2)
+    symbolic = torch.is_tensor(rayleigh) or torch.is_tensor(prandtl)
+    if symbolic:
+        P, R = '(Ra*Pr)**(-1/2)', '(Ra/Pr)**(-1/2)'
+    else:
+        P = (rayleigh * prandtl) ** (-1 / 2)
+        R = (rayleigh / prandtl) ** (-1 / 2)
     nt, nz, nx = 1. / t_crop, 1. / z_crop, 1. / x_crop
     equations = [
         ('transport_eqn_b', _transport('b', nt, nx, nz, P, '')),
@@ -51,7 +61,11 @@ def get_rb2_pde_layer(mean=None, std=None, t_crop=2., z_crop=1., x_crop=2., pran
                 len(mean), len(std)))
         subs_dict = {v: '{}*{}+{}'.format(v, std[i], mean[i]) for i, v in enumerate(_OUT)}
 
-    layer = PDELayer(in_vars='t, x, z', out_vars=', '.join(_OUT))
+    layer = PDELayer(in_vars='t, x, z', out_vars=', '.join(_OUT), param_vars='Ra, Pr' if symbolic else '')
     for name, eqn in equations:
         layer.add_equation(eqn, name, subs_dict=subs_dict)
+    if symbolic:
+        ref = rayleigh if torch.is_tensor(rayleigh) else prandtl
+        as_tensor = lambda v: v if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float32, device=ref.device)
+        layer.update_parameters({'Ra': as_tensor(rayleigh), 'Pr': as_tensor(prandtl)})
     return layer

@@ -102,13 +102,23 @@ def loss_sum(a, b, loss_type):
     return _LOSS_SUMS[loss_type](a, torch.zeros_like(a) if b is None else b)
 
 
+def _coefficient_leaves(pde_layer):
+    """The grad-requiring leaf tensors among the layer's coefficients (``PDELayer.update_parameters``), in declaration order."""
+    vals = getattr(pde_layer, "params", None) or {}
+    return [vals[s.name] for s in getattr(pde_layer, "param_vars", ()) if s.name in vals and vals[s.name].requires_grad
+            and vals[s.name].is_leaf]
+
+
 def sharded_step(unet, imnet, pde_layer, input_grid, point_coord, point_value, n_points_global, alpha_reg=1.0,
                  alpha_pde=1.0, loss_type="l1", xmin=0.0, xmax=1.0, distributed=None, sync_unet_grads=False):
     """Forward + backward of one step on this rank's slice of the query points.
 
     input_grid [b, c, T, Z, X] (identical on every rank); point_coord / point_value [b, n_local, 3|o] (this rank's
     slice); n_points_global = total points per batch element over all ranks.  Gradients are left in ``.grad`` of
-    the UNet / IM-NET parameters, already summed over ranks.  Returns (loss, reg_loss, pde_loss) global values.
+    the UNet / IM-NET parameters, already summed over ranks -- and of the layer's grad-requiring coefficient tensors
+    (``PDELayer.update_parameters``), whose gradients are sums over this rank's points: those that are leaves are summed over
+    ranks in one more small collective; a coefficient computed from a leaf (Ra = exp(log_Ra)) is refused in a distributed step,
+    since the leaf's gradient would stay per rank.  Returns (loss, reg_loss, pde_loss) global values.
     sync_unet_grads: the replicated UNet backward uses fp32 atomics, so its gradients agree across ranks only to
     rounding (~1e-7 relative); True averages them with one more all-reduce so that long runs keep the replicas
     bit-identical (the reference's DDP all-reduces every gradient, train_ddp.py:401-406).
@@ -117,6 +127,9 @@ def sharded_step(unet, imnet, pde_layer, input_grid, point_coord, point_value, n
         distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     if loss_type not in _LOSS_SUMS:
         raise KeyError(loss_type)
+    if distributed and any(t.requires_grad and not t.is_leaf for t in (getattr(pde_layer, "params", None) or {}).values()):
+        raise NotImplementedError("sharded_step(distributed=True): a grad-requiring equation coefficient must be a leaf tensor "
+                                  "(the gradient of a leaf behind it would not be summed over ranks)")
     # this step calls loss.backward() itself, so the U-Net's weight gradients may run beside its input-gradient chain
     # (unet3d._DeferredGrads, opt-in); the caller's setting of the flag is restored when the step is over
     prev_deferred = getattr(unet, "deferred_weight_grads", None)
@@ -181,6 +194,16 @@ def _sharded_step(unet, imnet, pde_layer, input_grid, point_coord, point_value, 
             g.copy_(flat[o:o + g.numel()].view_as(g))
             o += g.numel()
     if distributed:
+        # a coefficient's gradient is a sum over the points of THIS rank: one small collective for all of them
+        cg = [t.grad for t in _coefficient_leaves(pde_layer) if t.grad is not None]
+        if cg:
+            cflat = torch.cat([g.reshape(-1) for g in cg])
+            last_collectives.append(("equation coefficient gradients", cflat.numel() * 4))
+            dist.all_reduce(cflat)
+            o = 0
+            for g in cg:
+                g.copy_(cflat[o:o + g.numel()].view_as(g))
+                o += g.numel()
         if sync_unet_grads:
             ug = [p.grad for p in unet.parameters() if p.grad is not None]
             uflat = torch.cat([g.reshape(-1) for g in ug])
@@ -208,6 +231,7 @@ def data_parallel_step(unet, imnet, pde_layer, input_grid, point_coord, point_va
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         world = dist.get_world_size()
         grads = [p.grad for m in (unet, imnet) for p in m.parameters() if p.grad is not None]
+        grads += [t.grad for t in _coefficient_leaves(pde_layer) if t.grad is not None]
         flat = torch.cat([g.reshape(-1) for g in grads])
         dist.all_reduce(flat)
         flat /= world
@@ -236,6 +260,8 @@ class GraphedStep:
     allocates device memory or synchronises (include/stpde_hip.h), so nothing in it is illegal under capture; host-side
     decisions of the step (memory plan, kernel variants) depend on shapes only and are frozen at capture.  So is the operand
     precision of the U-Net's 3x3x3 convolutions (``unet3d.conv_precision``): a graph keeps the mode it was captured with.
+
+    A layer with tensor coefficients (``PDELayer(param_vars=...)``) is refused: capturing them is not implemented.
 
     Inputs are copied into static buffers before each replay; ``.grad`` of every parameter is a static tensor of the graph's
     memory pool, rewritten by each replay (``self.grads`` keeps them).  Not for a distributed step (collectives are not captured
@@ -278,6 +304,9 @@ class GraphedStep:
                                  "as None")
             input_grid, point_coord, point_value = sampler.lres, sampler.point_coord, sampler.point_value
         self.sampler = sampler
+        if getattr(pde_layer, "param_vars", ()):
+            raise NotImplementedError("GraphedStep does not take a PDELayer with tensor coefficients (param_vars): use "
+                                      "sharded_step, or give the layer numbers")
         if optimizer is not None and not (getattr(optimizer, "capturable", False) and all(
                 hasattr(optimizer, m) for m in ("prepare", "state_tensors", "sync_lr", "flush_tables"))):
             raise ValueError("GraphedStep(optimizer=...) needs a capturable optimizer of this package (FusedClipAdam / "

@@ -1,0 +1,297 @@
+"""Equation coefficients as tensors (PDELayer(param_vars=...), update_parameters), everything that needs no GPU: the residual
+compiler and programs of parameter-free layers (unchanged), both torch strategies of PDELayer with scalar and per-batch-element
+values, the error cases, get_rb2_pde_layer with numbers (unchanged) and with tensors, and the point-sharded step."""
+import base64
+import json
+import os
+import socket
+import sys
+import types
+
+import numpy as np
+import pytest
+import sympy
+import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
+
+from space_time_pde_amd import pde, physics
+from tests import residual_model as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+BURGERS = "dif(u,t)+u*dif(u,x)-nu*dif(dif(u,x),x)"
+MEAN, STD = (0.01, 0.0, 0.02, -0.01), (0.05, 0.3, 0.15, 0.12)
+C5_VARS = ("x, y, t", "c, u, v, w, p")
+C5_EQS = {
+    "adv_diff": "dif(c,t)+u*dif(c,x)+v*dif(c,y)-0.01*(dif(dif(c,x),x)+dif(dif(c,y),y))",
+    "prod_rule": "dif(u*c,x)+dif(v*c,y)",
+    "mixed": "dif(dif(c,x),y)-w*p",
+    "explicit_x": "x*dif(p,x)+t*dif(dif(p,t),t)",
+}
+
+
+def _parent():
+    with open(os.path.join(ROOT, "tests", "golden", "residual_programs_parent.json")) as f:
+        return json.load(f)
+
+
+def _compile(layer, combo):
+    """The layer's device program, compiled the way PDELayer._residues_hip compiles it: (program, uses_x, stream_of, progs)."""
+    progs = layer.eqns_jet
+    stream_of = {(): 0, (0,): 1, (1,): 2, (2,): 3}
+    if combo:
+        plan = layer._combo_plan()
+        assert plan is not None
+        progs = plan["progs"]
+        stream_of[("L",)] = 4
+    else:
+        pairs = sorted({mi for p in progs.values() for _, mi in p.atoms if len(mi) == 2})
+        for k, pr in enumerate(pairs):
+            stream_of[pr] = 4 + k
+    slots = {sym: (stream_of[k[1]], k[0]) for p in progs.values() for k, sym in p.syms.items()}
+    comp = pde._compile_residual_program([p.expr for p in progs.values()], list(layer.in_vars), slots)
+    return comp, stream_of, progs
+
+
+# ---- the compiler ---------------------------------------------------------------------------------------------------------------
+def test_res_ops_table_is_unchanged():
+    assert pde._RES_OPS == M.OPS and len(pde._RES_OPS) == 17
+    assert pde._RES_DT == M.DT
+
+
+def test_programs_without_parameters_are_byte_identical_to_the_parent_commits():
+    want = _parent()
+    layers = {
+        "rb2_bench": (physics.get_rb2_pde_layer(mean=MEAN, std=STD, t_crop=2., z_crop=1., x_crop=1., use_continuity=True), True),
+        "rb2_default": (physics.get_rb2_pde_layer(), True),
+        "rb2_ra1e5_pr07": (physics.get_rb2_pde_layer(prandtl=0.7, rayleigh=1e5, t_crop=4., z_crop=0.5, x_crop=3.,
+                                                     use_continuity=True), True),
+    }
+    c5 = pde.PDELayer(*C5_VARS)
+    for n, e in C5_EQS.items():
+        c5.add_equation(e, n)
+    layers["c5"] = (c5, False)
+    for key, (layer, combo) in layers.items():
+        assert layer.param_vars == () and layer.params == {}
+        assert layer.eqns_raw == want[key]["eqns_raw"], key                 # with numbers the strings are what they were
+        (prog, uses_x), _, _ = _compile(layer, combo)
+        assert prog.tobytes() == base64.b64decode(want[key]["program"]), key
+        assert len(prog) == want[key]["nins"] and bool(uses_x) == want[key]["uses_x"]
+    # the three-argument form still is the whole signature a parameter-free caller needs
+    j = sympy.Symbol("j")
+    prog, uses_x = pde._compile_residual_program([2 * j], [], {j: (0, 0)})
+    assert len(prog) == 4 and not uses_x
+
+
+# ---- PDELayer on the CPU ------------------------------------------------------------------------------------------------------
+class _Field:
+    """y_c = sin(a_c . x + b_c): values, first and second derivatives in closed form, any dtype."""
+
+    def __init__(self, n_in, n_out, dtype):
+        g = torch.Generator().manual_seed(11)
+        self.a = (0.5 + torch.rand(n_out, n_in, generator=g, dtype=torch.float64)).to(dtype)
+        self.b = torch.rand(n_out, generator=g, dtype=torch.float64).to(dtype)
+
+    def __call__(self, x):
+        return torch.sin(x @ self.a.t() + self.b)
+
+    def jets(self, x, pairs):
+        """[1 + 3 + len(pairs), n_out, P] in the stream order of PDELayer._residues_from_jets."""
+        ph = (x @ self.a.t() + self.b).reshape(-1, self.a.shape[0]).t()            # [n_out, P]
+        n_in = self.a.shape[1]
+        rows = [torch.sin(ph)]
+        for d in range(3):
+            rows.append(self.a[:, d:d + 1] * torch.cos(ph) if d < n_in else torch.zeros_like(ph))
+        for i, j in pairs:
+            rows.append(-(self.a[:, i:i + 1] * self.a[:, j:j + 1]) * torch.sin(ph))
+        return torch.stack(rows)
+
+
+def _both_strategies(layer, field, x, pairs):
+    """(generic residuals, jet-strategy residuals through the torch functions) of a layer on CPU tensors."""
+    layer.update_forward_method(field)
+    _, generic = layer(x.clone(), return_residue=True)
+    req = types.SimpleNamespace(jets=field.jets(x, pairs), pairs_out=[tuple(p) for p in pairs])
+    return generic, layer._residues_from_jets(x, req)
+
+
+@pytest.mark.parametrize("shape", ["scalar", "one", "batch"])
+def test_layer_on_cpu_both_strategies_values_and_coefficient_gradients(shape):
+    """Burgers with a learnable nu and a forcing amplitude, B = 3: both torch strategies against the fp64 evaluation of the same
+    lambdified equation, values and d loss / d coefficient."""
+    B, N = 3, 17
+    layer = pde.PDELayer("x, t", "u", "nu, amp")
+    layer.add_equation(BURGERS + "-amp*sin(x)", "burgers")
+    g = torch.Generator().manual_seed(2)
+    x = torch.rand(B, N, 2, generator=g)
+    cot = torch.randn(B, N, 1, generator=g)
+    make = {"scalar": lambda v: torch.tensor(v), "one": lambda v: torch.tensor([v]),
+            "batch": lambda v: v * torch.tensor([1.0, 2.0, 0.5])}[shape]
+    vals = {"nu": make(0.05).requires_grad_(True), "amp": make(0.3).requires_grad_(True)}
+    layer.update_parameters(vals)
+    grads = []
+    for which in (0, 1):
+        for t in vals.values():
+            t.grad = None
+        res = _both_strategies(layer, _Field(2, 1, torch.float32), x, [(0, 0)])[which]
+        assert list(res) == ["burgers"] and res["burgers"].shape == (B, N, 1)
+        (res["burgers"] * cot).sum().backward()
+        grads.append((res["burgers"].detach(), {k: t.grad.clone() for k, t in vals.items()}))
+    # fp64: the generic strategy on fp64 tensors
+    f64 = _Field(2, 1, torch.float64)
+    cols = [x.double()[..., i:i + 1].clone().requires_grad_(True) for i in range(2)]
+    y = f64(torch.cat(cols, -1))
+    v64 = {k: t.detach().double().requires_grad_(True) for k, t in vals.items()}
+    r64 = layer.eqns_fn["burgers"](*cols, y, *[v64[s.name].reshape(-1, 1, 1) for s in layer.param_vars])
+    (r64 * cot.double()).sum().backward()
+    for res, gr in grads:
+        assert torch.allclose(res.double(), r64.detach(), rtol=2e-5, atol=2e-5)
+        for k in vals:
+            assert gr[k].shape == vals[k].shape
+            assert torch.allclose(gr[k].double(), v64[k].grad, rtol=1e-4, atol=1e-5), (k, gr[k], v64[k].grad)
+
+
+def test_error_cases():
+    layer = pde.PDELayer("x, t", "u", "nu")
+    layer.add_equation(BURGERS, "burgers")
+    with pytest.raises(ValueError):
+        layer.add_equation("kappa*dif(u,x)", "unknown_symbol")
+    with pytest.raises(ValueError):
+        pde.PDELayer("x, t", "u").add_equation(BURGERS, "no_params_declared")
+    layer.update_forward_method(_Field(2, 1, torch.float32))
+    x = torch.rand(3, 5, 2)
+    with pytest.raises(RuntimeError):
+        layer(x)                                                            # unset
+    for bad in (torch.zeros(2, 2), torch.zeros(3, 1), torch.zeros(3, dtype=torch.float64)):
+        with pytest.raises(ValueError):
+            layer.update_parameters({"nu": bad})
+    with pytest.raises(ValueError):
+        layer.update_parameters({"mu": torch.tensor(1.0)})
+    layer.update_parameters({"nu": torch.zeros(4)})                          # [B] with another B than the query's
+    with pytest.raises(ValueError):
+        layer(x)
+    layer.update_parameters({"nu": torch.zeros(3)})
+    y, res = layer(x)
+    assert res["burgers"].shape == (3, 5, 1)
+    assert layer(x, return_residue=False).shape == (3, 5, 1)
+
+
+def test_default_layer_is_what_it_was():
+    layer = pde.PDELayer("x, y, t", "u, v")
+    assert layer.param_vars == () and layer.params == {} and layer.all_vars == list(layer.in_vars) + list(layer.out_vars)
+    layer.add_equation("dif(u,x)+dif(v,y)", "div", subs_dict={"u": "2*u"})
+    assert layer.eqns_raw == {"div": "dif(u,x)+dif(v,y)"} and layer.eqn_names == ["div"] and layer.eqn_num == 1
+
+
+# ---- get_rb2_pde_layer ----------------------------------------------------------------------------------------------------------
+def test_rb2_layer_with_tensors_keeps_the_combined_stream_and_matches_the_constant_layers():
+    Ra, Pr = torch.tensor([1e6, 1e5]), torch.tensor(0.5)
+    layer = physics.get_rb2_pde_layer(mean=MEAN, std=STD, t_crop=2., z_crop=1., x_crop=1., prandtl=Pr, rayleigh=Ra,
+                                      use_continuity=True)
+    assert [s.name for s in layer.param_vars] == ["Ra", "Pr"] and layer.params["Ra"] is Ra and layer.params["Pr"] is Pr
+    assert "(Ra*Pr)**(-1/2)" in layer.eqns_raw["transport_eqn_b"] and "(Ra/Pr)**(-1/2)" in layer.eqns_raw["transport_eqn_u"]
+    const = [physics.get_rb2_pde_layer(mean=MEAN, std=STD, t_crop=2., z_crop=1., x_crop=1., prandtl=0.5, rayleigh=r,
+                                       use_continuity=True) for r in (1e6, 1e5)]
+    plan = layer._combo_plan()
+    assert plan is not None and plan["alpha"] == const[0]._combo_plan()["alpha"]
+    comp, stream_of, progs = _compile(layer, True)
+    assert comp is None                       # the device evaluator reads constants only: such a layer takes the torch functions
+    # the jet strategy's torch functions, B = 2 with a different Ra per element, against the constant-coefficient layers
+    g = torch.Generator().manual_seed(4)
+    x = torch.rand(2, 9, 3, generator=g, dtype=torch.float64)
+    jets = torch.randn(5, 4, 18, generator=g, dtype=torch.float64)
+    layer.params = {"Ra": Ra.double(), "Pr": Pr.double()}
+    req = types.SimpleNamespace(jets=jets, pairs_out=["combo"])
+    res = layer._residues_from_jets(x, req)
+    for b, lc in enumerate(const):
+        want = lc._residues_from_jets(x, req)
+        for k in want:
+            assert torch.allclose(res[k][b], want[k][b], rtol=1e-12, atol=1e-12), (b, k)
+
+
+def test_rb2_layer_with_one_tensor_and_one_number():
+    layer = physics.get_rb2_pde_layer(rayleigh=torch.tensor([1e6]), prandtl=2.0)
+    assert layer.params["Pr"].dtype == torch.float32 and layer.params["Pr"].item() == 2.0
+
+
+def test_distributed_step_refuses_a_non_leaf_coefficient():
+    from space_time_pde_amd.train_step import sharded_step
+    log_nu = torch.tensor(-3.0, requires_grad=True)
+    layer = pde.PDELayer("x, t", "u", "nu")
+    layer.update_parameters({"nu": log_nu.exp()})
+    with pytest.raises(NotImplementedError):
+        sharded_step(None, None, layer, None, None, None, 1, distributed=True)
+
+
+def test_graphed_step_refuses_a_layer_with_tensor_coefficients():
+    from space_time_pde_amd.train_step import GraphedStep
+    layer = pde.PDELayer("x, t", "u", "nu")
+    with pytest.raises(NotImplementedError):
+        GraphedStep(None, None, layer, None, None, None, 1)
+
+
+# ---- the point-sharded step -------------------------------------------------------------------------------------------------------
+@pytest.fixture
+def restore_num_threads():
+    prev = torch.get_num_threads()
+    yield
+    torch.set_num_threads(prev)
+
+
+def _build(tensors=True):
+    from space_time_pde_amd import implicit_net, unet3d
+    torch.manual_seed(0)
+    unet = unet3d.UNet3d(in_features=4, out_features=32, igres=(4, 4, 4), nf=4, mf=8)
+    unet.eval()
+    imnet = implicit_net.ImNet(dim=3, in_features=32, out_features=4, nf=4, activation=torch.nn.Softplus)
+    Ra = torch.tensor([1e4]).requires_grad_(True) if tensors else 1e4
+    Pr = torch.tensor(0.7).requires_grad_(True) if tensors else 0.7
+    layer = physics.get_rb2_pde_layer(mean=MEAN, std=STD, t_crop=2., z_crop=1., x_crop=1., prandtl=Pr, rayleigh=Ra,
+                                      use_continuity=True)
+    g = torch.Generator().manual_seed(1)
+    crop = torch.randn(1, 4, 4, 4, 4, generator=g)
+    pts = 0.05 + 0.9 * torch.rand(1, 64, 3, generator=g)
+    tgt = torch.randn(1, 64, 4, generator=g)
+    return unet, imnet, layer, crop, pts, tgt, Ra, Pr
+
+
+def _worker(rank, world, port, out):
+    sys.path.insert(0, ROOT)
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    torch.set_num_threads(1)
+    from space_time_pde_amd import train_step
+    names = {}
+    for tensors in (False, True):
+        unet, imnet, layer, crop, pts, tgt, Ra, Pr = _build(tensors)
+        n = pts.shape[1] // world
+        sl = slice(rank * n, (rank + 1) * n)
+        loss, reg, pde_ = train_step.sharded_step(unet, imnet, layer, crop, pts[:, sl], tgt[:, sl], pts.shape[1], 1.0, 1.0)
+        names[tensors] = list(train_step.last_collectives)
+    if rank == 0:
+        torch.save(dict(loss=loss, g_ra=Ra.grad, g_pr=Pr.grad, names=names), out)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_two_rank_coefficient_gradients_equal_single_process(tmp_path, restore_num_threads):
+    from space_time_pde_amd.train_step import sharded_step
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    out = str(tmp_path / "rank0.pt")
+    mp.spawn(_worker, args=(2, port, out), nprocs=2, join=True)
+    got = torch.load(out)
+    torch.set_num_threads(1)
+    unet, imnet, layer, crop, pts, tgt, Ra, Pr = _build(True)
+    loss, _, _ = sharded_step(unet, imnet, layer, crop, pts, tgt, pts.shape[1], 1.0, 1.0, distributed=False)
+    assert abs(got["loss"].item() - loss.item()) < 1e-6 * abs(loss.item())
+    assert Ra.grad.shape == (1,) and Pr.grad.shape == () and Ra.grad.abs().item() > 0 and Pr.grad.abs().item() > 0
+    assert (got["g_ra"] - Ra.grad).abs().max() <= 2e-5 * Ra.grad.abs().max()
+    assert (got["g_pr"] - Pr.grad).abs().max() <= 2e-5 * Pr.grad.abs().max()
+    coeff = [c for c in got["names"][True] if c[0] == "equation coefficient gradients"]
+    assert coeff == [("equation coefficient gradients", 8)]                  # one collective: Ra [1] and Pr []
+    assert [c for c in got["names"][True] if c not in coeff] == got["names"][False]    # without coefficients: what it was

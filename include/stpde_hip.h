@@ -649,13 +649,24 @@ int stpde_resample3d(const stpde_resample_desc* d, int mode, const float* in, co
  *   X     value = x[p][a]            CONST value = c
  *   ADD SUB MUL DIV (a, b)   NEG (a)   POWI value = v[a]^b (integer b)   SIN COS EXP LOG SQRT TANH ABS (a)
  *   OUT   residual b of the point = v[a]
+ * Appended after OUT (nothing above is renumbered; values and adjoints follow torch and its autograd):
+ *   TAN SINH COSH ASIN ACOS ATAN (a)   ATAN2 value = atan2(v[a], v[b])
+ *   POWC  value = v[a]^c (real constant c: its integer part by POWI's multiplications, the fraction through powf, so an
+ *         integral c is exact); adjoint c * v[a]^(c-1), never divided by v[a]: v[a] = 0 is regular for c >= 1
+ *   POW   value = v[a]^v[b]; adjoints as torch.pow (0 into the base where v[b] == 0, 0 into the exponent where
+ *         v[a] == 0 and v[b] >= 0)
+ *   MIN MAX (a, b)  NaN propagates; on a tie each operand receives half the cotangent (torch.minimum / maximum)
+ *   SIGN (a)  sign(0) = 0, sign(NaN) = NaN     STEP (a)  Heaviside with H(0) = 1/2, H(NaN) = NaN; both have adjoint 0
+ * MIN MAX SIGN STEP are fixed IEEE sequences like ABS; the others go through the device's math library.
  * res [n_eq][P]; the adjoint adds d loss / d jets into jets_bar (same layout as jets, zero-filled by the caller).
  * The coordinates x are not differentiated here (the jets already are the coordinate derivatives). */
 #define STPDE_RES_MAX_INS 192
 enum {
   STPDE_RES_JET = 0, STPDE_RES_X, STPDE_RES_CONST, STPDE_RES_ADD, STPDE_RES_SUB, STPDE_RES_MUL, STPDE_RES_DIV,
   STPDE_RES_NEG, STPDE_RES_POWI, STPDE_RES_SIN, STPDE_RES_COS, STPDE_RES_EXP, STPDE_RES_LOG, STPDE_RES_SQRT,
-  STPDE_RES_TANH, STPDE_RES_ABS, STPDE_RES_OUT
+  STPDE_RES_TANH, STPDE_RES_ABS, STPDE_RES_OUT,
+  STPDE_RES_TAN, STPDE_RES_SINH, STPDE_RES_COSH, STPDE_RES_ASIN, STPDE_RES_ACOS, STPDE_RES_ATAN, STPDE_RES_ATAN2,
+  STPDE_RES_POWC, STPDE_RES_POW, STPDE_RES_MIN, STPDE_RES_MAX, STPDE_RES_SIGN, STPDE_RES_STEP
 };
 typedef struct {
   int op, a, b;

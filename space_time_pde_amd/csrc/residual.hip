@@ -19,7 +19,49 @@ struct ResArgs {
   float* jets_bar;             // same layout as jets, zero-filled by the caller
 };
 
+// x^c for a real constant c = n + f, n = trunc(c): the integer part by POWI's own square-and-multiply (and 1 / r for n < 0), the
+// fraction through powf.  An integral c -- c = 1, or the c - 1 = 0 of its adjoint -- then costs no rounding of the math library
+// (its powf(x, 1) is not x in every bit), and the result keeps pow's conventions: NaN for x < 0 unless f = 0, the sign of x for an
+// odd integral c, +0 / +Inf at x = -0 otherwise (hence |x| under the integer part when f != 0).
+__device__ __forceinline__ float res_powc(float x, float c) {
+  const float n = truncf(c), f = c - n;
+  if (fabsf(n) > 64.f) return powf(x, c);
+  float base = f != 0.f ? fabsf(x) : x, r = 1.f;
+  const int ni = (int)n;
+  int e = ni < 0 ? -ni : ni;
+  while (e) {
+    if (e & 1) r *= base;
+    base *= base;
+    e >>= 1;
+  }
+  if (ni < 0) r = 1.f / r;
+  return f != 0.f ? r * powf(x, f) : r;
+}
+
+// The opcodes appended after OUT.  They are kept out of the switch of the first 17 (one comparison in front of it instead of
+// thirteen more cases in it): the programs of the equations that compiled before hold none of them.
+__device__ __forceinline__ float res_eval_ext(const stpde_res_ins& in, const float* v) {
+  switch (in.op) {
+    case STPDE_RES_TAN: return tanf(v[in.a]);
+    case STPDE_RES_SINH: return sinhf(v[in.a]);
+    case STPDE_RES_COSH: return coshf(v[in.a]);
+    case STPDE_RES_ASIN: return asinf(v[in.a]);
+    case STPDE_RES_ACOS: return acosf(v[in.a]);
+    case STPDE_RES_ATAN: return atanf(v[in.a]);
+    case STPDE_RES_ATAN2: return atan2f(v[in.a], v[in.b]);
+    case STPDE_RES_POWC: return res_powc(v[in.a], in.c);
+    case STPDE_RES_POW: return powf(v[in.a], v[in.b]);
+    // MIN MAX SIGN STEP: comparisons and selects only; every comparison is false for NaN, which the last operand then carries
+    case STPDE_RES_MIN: { const float x = v[in.a], y = v[in.b]; return (x < y || x != x) ? x : y; }
+    case STPDE_RES_MAX: { const float x = v[in.a], y = v[in.b]; return (x > y || x != x) ? x : y; }
+    case STPDE_RES_SIGN: { const float x = v[in.a]; return x > 0.f ? 1.f : (x < 0.f ? -1.f : (x == 0.f ? 0.f : x)); }
+    case STPDE_RES_STEP: { const float x = v[in.a]; return x > 0.f ? 1.f : (x < 0.f ? 0.f : (x == 0.f ? 0.5f : x)); }
+    default: return v[in.a];
+  }
+}
+
 __device__ __forceinline__ float res_eval(const stpde_res_ins& in, const float* v, const ResArgs& a, int p) {
+  if (in.op > STPDE_RES_OUT) return res_eval_ext(in, v);
   switch (in.op) {
     case STPDE_RES_JET: return a.jets[(size_t)in.a * a.ld_s + (size_t)in.b * a.ld_c + p];
     case STPDE_RES_X: return a.x[(size_t)p * 3 + in.a];
@@ -64,6 +106,50 @@ __global__ __launch_bounds__(256) void k_residual_fwd(ResArgs a) {
   }
 }
 
+// Reverse rules of the appended opcodes (instruction i, its adjoint gi).
+__device__ __forceinline__ void res_bwd_ext(const stpde_res_ins& in, int i, const float* v, float* g, float gi) {
+  switch (in.op) {
+    case STPDE_RES_TAN: g[in.a] += gi * (1.f + v[i] * v[i]); break;
+    case STPDE_RES_SINH: g[in.a] += gi * coshf(v[in.a]); break;
+    case STPDE_RES_COSH: g[in.a] += gi * sinhf(v[in.a]); break;
+    case STPDE_RES_ASIN: g[in.a] += gi / sqrtf(1.f - v[in.a] * v[in.a]); break;
+    case STPDE_RES_ACOS: g[in.a] -= gi / sqrtf(1.f - v[in.a] * v[in.a]); break;
+    case STPDE_RES_ATAN: g[in.a] += gi / (1.f + v[in.a] * v[in.a]); break;
+    case STPDE_RES_ATAN2: {
+      const float x = v[in.a], y = v[in.b], d = x * x + y * y;
+      const bool origin = x == 0.f && y == 0.f;      // torch: no gradient there
+      g[in.a] += origin ? 0.f : gi * y / d;
+      g[in.b] -= origin ? 0.f : gi * x / d;
+      break;
+    }
+    case STPDE_RES_POWC: {   // c x^(c-1) without dividing by x; c - 1 is taken in double like torch's scalar exponent
+      if (in.c != 0.f) g[in.a] += gi * (in.c * res_powc(v[in.a], (float)((double)in.c - 1.0)));
+      break;
+    }
+    case STPDE_RES_POW: {    // torch.pow: nothing into the base where y == 0, nothing into the exponent where x == 0 and y >= 0
+      const float x = v[in.a], y = v[in.b];
+      const float gx = y == 0.f ? 0.f : gi * (y * powf(x, y - 1.f));
+      const float gy = gi * ((x == 0.f && y >= 0.f) ? 0.f : v[i] * logf(x));
+      g[in.a] += gx;
+      g[in.b] += gy;
+      break;
+    }
+    case STPDE_RES_MIN: {    // torch.minimum: the smaller operand takes the cotangent, a tie halves it, NaN passes it to both
+      const float x = v[in.a], y = v[in.b], h = x == y ? gi * 0.5f : gi;
+      g[in.a] += x > y ? 0.f : h;
+      g[in.b] += x < y ? 0.f : h;
+      break;
+    }
+    case STPDE_RES_MAX: {
+      const float x = v[in.a], y = v[in.b], h = x == y ? gi * 0.5f : gi;
+      g[in.a] += x < y ? 0.f : h;
+      g[in.b] += x > y ? 0.f : h;
+      break;
+    }
+    default: break;   // SIGN, STEP: adjoint 0
+  }
+}
+
 __global__ __launch_bounds__(256) void k_residual_bwd(ResArgs a) {
   __shared__ stpde_res_ins prog[RES_MAX];
   for (int i = threadIdx.x; i < a.nins; i += 256) prog[i] = a.prog[i];
@@ -78,6 +164,10 @@ __global__ __launch_bounds__(256) void k_residual_bwd(ResArgs a) {
   for (int i = a.nins - 1; i >= 0; --i) {
     const stpde_res_ins in = prog[i];
     float gi = g[i];
+    if (in.op > STPDE_RES_OUT) {
+      res_bwd_ext(in, i, v, g, gi);
+      continue;
+    }
     switch (in.op) {
       case STPDE_RES_OUT: g[in.a] += a.res_bar[(size_t)in.b * a.P + p]; break;
       case STPDE_RES_JET: {

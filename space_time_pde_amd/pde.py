@@ -16,6 +16,11 @@ Two evaluation strategies:
   elementwise algebra on them.  If the forward method is anything else (or post-processes the query result) the
   generic strategy is used, exactly like the reference.
 
+Functions (beyond the reference's lambdify defaults): Max / Min of any arity, sign, Heaviside (H(0) = 1/2), Abs under a ``dif``
+(``dif(Abs(f), x)`` = sign(f) f_x), real and expression powers, tan sinh cosh asin acos atan atan2 evaluate elementwise on tensors
+on every strategy with torch's conventions (ties halve the cotangent, NaN propagates, sign' = H' = 0), and compile into the device
+residual program (``_compile_residual_program(..., extended=True)``, opcodes ``_RES_OPS_EXT``); DESIGN section 9 has the envelope.
+
 Coefficients (an extension of the reference surface): ``PDELayer(in_vars, out_vars, param_vars='nu')`` declares symbols whose
 values are tensors handed over with ``update_parameters`` -- one value for all points or one per batch element, optionally
 requiring grad (inverse problems, mixed-regime batches).  Both torch strategies take them.  The HIP residual evaluator does
@@ -29,6 +34,7 @@ import sympy
 import torch
 from sympy.core.function import AppliedUndef
 from sympy.parsing.sympy_parser import parse_expr
+from sympy.printing.pycode import PythonCodePrinter
 from torch.autograd import grad
 
 from . import _lib
@@ -40,8 +46,88 @@ def torch_diff(y, x):
     return grad(y, x, grad_outputs=torch.ones_like(y), create_graph=True, allow_unused=True)[0]
 
 
+def _tensor_args(args):
+    """Numbers among the arguments of a two-tensor torch function (``Max(u, 0)``, ``atan2(u, 1)``) as 0-d tensors of the
+    dtype and device of the first tensor argument."""
+    ref = next((a for a in args if torch.is_tensor(a)), None)
+    if ref is None:
+        return [torch.as_tensor(float(a)) for a in args]
+    return [a if torch.is_tensor(a) else torch.as_tensor(float(a), dtype=ref.dtype, device=ref.device) for a in args]
+
+
+def _t_max(*args):
+    """``Max(a, b, ...)``: a chain of torch.maximum (NaN propagates, a tie halves the cotangent) from left to right."""
+    args = _tensor_args(args)
+    r = args[0]
+    for a in args[1:]:
+        r = torch.maximum(r, a)
+    return r
+
+
+def _t_min(*args):
+    args = _tensor_args(args)
+    r = args[0]
+    for a in args[1:]:
+        r = torch.minimum(r, a)
+    return r
+
+
+def _t_sign(a):
+    """torch.sign (sign(0) = 0, gradient 0) with sign(NaN) = NaN: torch's own gives 0 there."""
+    a, = _tensor_args([a])
+    return torch.where(a != a, a.detach(), torch.sign(a))
+
+
+def _t_heaviside(a, h0=0.5):
+    """sympy's Heaviside: 1, 0, H(0) = h0 (1/2 by default: the tie rule of Max / Min), NaN for NaN; gradient 0."""
+    a, = _tensor_args([a])
+    s = _t_sign(a)
+    return torch.where(a == 0, torch.as_tensor(float(h0), dtype=a.dtype, device=a.device), 0.5 * (s + 1.0))
+
+
+def _t_atan2(a, b):
+    return torch.atan2(*_tensor_args([a, b]))
+
+
 _TORCH_FUNCS = {"sin": torch.sin, "cos": torch.cos, "tan": torch.tan, "exp": torch.exp, "log": torch.log,
-                "sqrt": torch.sqrt, "tanh": torch.tanh, "sinh": torch.sinh, "cosh": torch.cosh, "Abs": torch.abs}
+                "sqrt": torch.sqrt, "tanh": torch.tanh, "sinh": torch.sinh, "cosh": torch.cosh, "Abs": torch.abs,
+                "asin": torch.asin, "acos": torch.acos, "atan": torch.atan, "atan2": _t_atan2, "Max": _t_max, "Min": _t_min,
+                "sign": _t_sign, "Heaviside": _t_heaviside}
+
+
+class _TorchPrinter(PythonCodePrinter):
+    """The printer sympy.lambdify picks for these modules, except that Max, Min, sign and Heaviside print as calls of the
+    elementwise functions above: as Python conditionals (the stock printer) they cannot take tensors."""
+
+    def _call(self, e):
+        return "%s(%s)" % (e.func.__name__, ", ".join(self._print(a) for a in e.args))
+
+    _print_Max = _print_Min = _print_sign = _print_Heaviside = _call
+
+
+def _lambdify(args, expr, extra=None):
+    """sympy.lambdify onto the torch functions (and ``extra``, e.g. dif), with the settings lambdify gives its own printer."""
+    modules = ([extra] if extra else []) + [_TORCH_FUNCS]
+    names = {k: k for m in modules for k in m}
+    printer = _TorchPrinter({'fully_qualified_modules': False, 'inline': True, 'allow_unknown_functions': True,
+                             'user_functions': names})
+    return sympy.lambdify(args, expr, modules, printer=printer)
+
+
+class _RealSign(sympy.Function):
+    """sign of a real argument while PDELayer._compile_jet differentiates: derivative 0, as torch.sign's."""
+    nargs = 1
+
+    def fdiff(self, argindex=1):
+        return sympy.S.Zero
+
+
+class _RealAbs(sympy.Function):
+    """Abs of a real argument while PDELayer._compile_jet differentiates: d|f| = sign(f) df."""
+    nargs = 1
+
+    def fdiff(self, argindex=1):
+        return _RealSign(self.args[0])
 
 
 class _JetProgram:
@@ -59,6 +145,12 @@ _RES_OPS = {"JET": 0, "X": 1, "CONST": 2, "ADD": 3, "SUB": 4, "MUL": 5, "DIV": 6
             "EXP": 11, "LOG": 12, "SQRT": 13, "TANH": 14, "ABS": 15, "OUT": 16}
 _RES_UNARY = {sympy.sin: "SIN", sympy.cos: "COS", sympy.exp: "EXP", sympy.log: "LOG", sympy.tanh: "TANH",
               sympy.Abs: "ABS"}
+# appended after OUT (include/stpde_hip.h); only programs compiled with extended=True hold them
+_RES_OPS_EXT = {"TAN": 17, "SINH": 18, "COSH": 19, "ASIN": 20, "ACOS": 21, "ATAN": 22, "ATAN2": 23, "POWC": 24, "POW": 25,
+                "MIN": 26, "MAX": 27, "SIGN": 28, "STEP": 29}
+_RES_UNARY_EXT = {sympy.tan: "TAN", sympy.sinh: "SINH", sympy.cosh: "COSH", sympy.asin: "ASIN", sympy.acos: "ACOS",
+                  sympy.atan: "ATAN", sympy.sign: "SIGN"}
+_RES_OPS_ALL = dict(_RES_OPS, **_RES_OPS_EXT)
 _RES_MAX_INS = 192      # STPDE_RES_MAX_INS
 _RES_DT = np.dtype([("op", "<i4"), ("a", "<i4"), ("b", "<i4"), ("c", "<f4")])   # = stpde_res_ins
 
@@ -67,16 +159,43 @@ class _Unsupported(Exception):
     pass
 
 
-def _compile_residual_program(exprs, in_vars, sym_to_slot):
+def _compile_residual_program(exprs, in_vars, sym_to_slot, extended=False):
     """Straight-line SSA program (common sub-expressions shared) for a list of sympy expressions.
 
     sym_to_slot: {sympy symbol: (stream, channel)} for the jet atoms.  Returns (numpy program, uses_x) or None when
-    an expression contains something the device evaluator does not implement."""
+    an expression contains something the device evaluator does not implement.  extended: also use the opcodes of
+    _RES_OPS_EXT, for what the 17 of _RES_OPS cannot express (Max / Min as a chain, sign, Heaviside with H(0) = 1/2, real
+    and expression exponents, tan sinh cosh asin acos atan atan2); what compiles without them compiles to the same bytes."""
     ins, memo, uses_x = [], {}, [False]
 
     def emit(op, a=0, b=0, c=0.0):
-        ins.append((_RES_OPS[op], int(a), int(b), float(c)))
+        ins.append((_RES_OPS_ALL[op], int(a), int(b), float(c)))
         return len(ins) - 1
+
+    def rec_ext(e):
+        """What only the extended opcodes express."""
+        if e.is_Pow:
+            base, ex = e.args
+            if ex.is_Float and float(ex).is_integer():
+                return emit("POWI", rec(base), int(ex))             # u**2.0: the exact integer power
+            if ex.is_Number:
+                if not (ex.is_real and ex.is_finite):
+                    raise _Unsupported(e)
+                return emit("POWC", rec(base), c=float(ex))
+            return emit("POW", rec(base), rec(ex))
+        if e.func in (sympy.Max, sympy.Min):
+            op = "MAX" if e.func is sympy.Max else "MIN"
+            idx = rec(e.args[0])
+            for t in e.args[1:]:
+                idx = emit(op, idx, rec(t))
+            return idx
+        if e.func is sympy.Heaviside and (len(e.args) == 1 or e.args[1] == sympy.Rational(1, 2)):
+            return emit("STEP", rec(e.args[0]))
+        if e.func is sympy.atan2:
+            return emit("ATAN2", rec(e.args[0]), rec(e.args[1]))
+        if e.func in _RES_UNARY_EXT and len(e.args) == 1:
+            return emit(_RES_UNARY_EXT[e.func], rec(e.args[0]))
+        raise _Unsupported(e)
 
     def rec(e):
         if e in memo:
@@ -129,10 +248,14 @@ def _compile_residual_program(exprs, in_vars, sym_to_slot):
                 idx = emit("SQRT", rec(base))
             elif ex == -sympy.Rational(1, 2):
                 idx = emit("DIV", emit("CONST", c=1.0), emit("SQRT", rec(base)))
+            elif extended:
+                idx = rec_ext(e)
             else:
                 raise _Unsupported(e)
         elif e.func in _RES_UNARY and len(e.args) == 1:
             idx = emit(_RES_UNARY[e.func], rec(e.args[0]))
+        elif extended:
+            idx = rec_ext(e)
         else:
             raise _Unsupported(e)
         memo[e] = idx
@@ -243,7 +366,7 @@ class PDELayer(object):
             raise ValueError('Variables in the eqn_str ({}) does not match that of '
                              'in_vars ({}), out_vars ({}) and param_vars ({})'.format(
                                  expr.free_symbols, set(self.in_vars), set(self.out_vars), set(self.param_vars)))
-        fn = sympy.lambdify(self.all_vars + list(self.param_vars), expr, [{'dif': torch_diff}, _TORCH_FUNCS])
+        fn = _lambdify(self.all_vars + list(self.param_vars), expr, {'dif': torch_diff})
         self.eqns_raw.update({eqn_name: eqn_str})
         self.eqns_fn.update({eqn_name: fn})
         self.eqns_jet.update({eqn_name: self._compile_jet(expr)})
@@ -304,7 +427,7 @@ class PDELayer(object):
                 atoms = [(k, v) for k, v in prog.syms.items() if len(k[1]) < 2] + \
                         [((c, ("L",)), v) for c, v in lam.items()]
                 atoms.sort(key=lambda a: (a[0][0], len(a[0][1]), str(a[0][1])))
-                fn = sympy.lambdify(list(self.in_vars) + list(self.param_vars) + [a[1] for a in atoms], e, [_TORCH_FUNCS])
+                fn = _lambdify(list(self.in_vars) + list(self.param_vars) + [a[1] for a in atoms], e)
                 new[name] = _JetProgram(fn, [a[0] for a in atoms], e, {a[0]: a[1] for a in atoms})
             self._combo = dict(alpha=alpha, progs=new)
         except Exception as exc:   # any sympy corner case -> one stream per pair (never wrong, only slower)
@@ -320,7 +443,16 @@ class PDELayer(object):
             dif = sympy.Function('dif')
             e = e.replace(lambda t: isinstance(t, AppliedUndef) and t.func == dif and len(t.args) == 2,
                           lambda t: sympy.Derivative(t.args[0], t.args[1]))
+            # Abs, sign and Heaviside differentiate as the real functions torch's autograd sees (|f|' = sign(f) f', sign' = H' = 0):
+            # sympy expands the derivative of an Abs whose argument is not known to be real into re / im terms
+            real = e.has(sympy.Abs, sympy.sign)
+            if real:
+                e = e.replace(sympy.Abs, _RealAbs).replace(sympy.sign, _RealSign)
             e = e.doit()
+            if real:
+                e = e.replace(_RealAbs, sympy.Abs).replace(_RealSign, sympy.sign)
+            if e.has(sympy.DiracDelta):
+                e = e.replace(lambda t: isinstance(t, sympy.DiracDelta), lambda t: sympy.S.Zero)
             if e.has(dif) or e.has(sympy.Subs):
                 return None
             fout = {f: i for i, f in enumerate(funcs.values())}
@@ -348,7 +480,7 @@ class PDELayer(object):
             if e.atoms(AppliedUndef):
                 return None
             atoms.sort(key=lambda a: (a[0][0], len(a[0][1]), a[0][1]))
-            fn = sympy.lambdify(list(self.in_vars) + list(self.param_vars) + [a[1] for a in atoms], e, [_TORCH_FUNCS])
+            fn = _lambdify(list(self.in_vars) + list(self.param_vars) + [a[1] for a in atoms], e)
             return _JetProgram(fn, [a[0] for a in atoms], e, {a[0]: a[1] for a in atoms})
         except Exception as exc:  # any sympy corner case -> generic strategy (never wrong, only slower)
             _note_fallback("jet_compile_errors", "equation %s could not be expanded into jets (%r): reverse-sweep strategy"
@@ -474,7 +606,7 @@ class PDELayer(object):
             for prog in progs.values():
                 for akey, sym in prog.syms.items():
                     slots[sym] = (stream_of[akey[1]], akey[0])
-            comp = _compile_residual_program([p.expr for p in progs.values()], list(self.in_vars), slots)
+            comp = _compile_residual_program([p.expr for p in progs.values()], list(self.in_vars), slots, extended=True)
             ent = None
             if comp is not None:
                 arr, uses_x = comp

@@ -658,6 +658,16 @@ int stpde_resample3d(const stpde_resample_desc* d, int mode, const float* in, co
  *   MIN MAX (a, b)  NaN propagates; on a tie each operand receives half the cotangent (torch.minimum / maximum)
  *   SIGN (a)  sign(0) = 0, sign(NaN) = NaN     STEP (a)  Heaviside with H(0) = 1/2, H(NaN) = NaN; both have adjoint 0
  * MIN MAX SIGN STEP are fixed IEEE sequences like ABS; the others go through the device's math library.
+ * Appended after STEP (Piecewise with relational conditions; comparisons and selects only, fixed IEEE sequences):
+ *   LT LE EQ NE (a, b)  mask = 1.0 where v[a] < / <= / == / != v[b], else 0.0 (a NaN operand: 0.0, for NE 1.0); > and >= are
+ *         LT and LE with a and b swapped
+ *   AND OR (a, b)  NOT (a)  on masks (an operand counts as true where it is != 0); the result is 1.0 or 0.0, never NaN
+ *   SEL   value = v[a] != 0 ? v[then] : v[else], the two value indices packed into b: then = b & 0xffff, else = b >> 16
+ *         (STPDE_RES_SEL_THEN / _ELSE; indices are below STPDE_RES_MAX_INS).  Both operands are evaluated.  Adjoint as
+ *         torch.where: the selected operand receives the cotangent, the other exactly +0 (a select, not a product with the
+ *         mask: a NaN cotangent does not reach the operand not taken), nothing reaches the mask
+ *   STEPC (a)  Heaviside with H(0) = c, H(NaN) = NaN (STEP's c is 0 and means 1/2)
+ *   Masks, comparison operands and STEPC have adjoint 0.
  * res [n_eq][P]; the adjoint adds d loss / d jets into jets_bar (same layout as jets, zero-filled by the caller).
  * The coordinates x are not differentiated here (the jets already are the coordinate derivatives). */
 #define STPDE_RES_MAX_INS 192
@@ -668,6 +678,12 @@ enum {
   STPDE_RES_TAN, STPDE_RES_SINH, STPDE_RES_COSH, STPDE_RES_ASIN, STPDE_RES_ACOS, STPDE_RES_ATAN, STPDE_RES_ATAN2,
   STPDE_RES_POWC, STPDE_RES_POW, STPDE_RES_MIN, STPDE_RES_MAX, STPDE_RES_SIGN, STPDE_RES_STEP
 };
+enum { /* continues the list above */
+  STPDE_RES_LT = STPDE_RES_STEP + 1, STPDE_RES_LE, STPDE_RES_EQ, STPDE_RES_NE, STPDE_RES_AND, STPDE_RES_OR, STPDE_RES_NOT,
+  STPDE_RES_SEL, STPDE_RES_STEPC
+};
+#define STPDE_RES_SEL_THEN(b) ((int)((unsigned)(b) & 0xffffu))
+#define STPDE_RES_SEL_ELSE(b) ((int)((unsigned)(b) >> 16))
 typedef struct {
   int op, a, b;
   float c;

@@ -39,7 +39,7 @@ __device__ __forceinline__ float res_powc(float x, float c) {
 }
 
 // The opcodes appended after OUT.  They are kept out of the switch of the first 17 (one comparison in front of it instead of
-// thirteen more cases in it): the programs of the equations that compiled before hold none of them.
+// twenty-two more cases in it): the programs of the equations that compiled before hold none of them.
 __device__ __forceinline__ float res_eval_ext(const stpde_res_ins& in, const float* v) {
   switch (in.op) {
     case STPDE_RES_TAN: return tanf(v[in.a]);
@@ -56,6 +56,16 @@ __device__ __forceinline__ float res_eval_ext(const stpde_res_ins& in, const flo
     case STPDE_RES_MAX: { const float x = v[in.a], y = v[in.b]; return (x > y || x != x) ? x : y; }
     case STPDE_RES_SIGN: { const float x = v[in.a]; return x > 0.f ? 1.f : (x < 0.f ? -1.f : (x == 0.f ? 0.f : x)); }
     case STPDE_RES_STEP: { const float x = v[in.a]; return x > 0.f ? 1.f : (x < 0.f ? 0.f : (x == 0.f ? 0.5f : x)); }
+    // Masks, 1.0 or 0.0 and never NaN: IEEE comparisons (a NaN operand gives false, true for NE); AND OR NOT read a mask as != 0
+    case STPDE_RES_LT: return v[in.a] < v[in.b] ? 1.f : 0.f;
+    case STPDE_RES_LE: return v[in.a] <= v[in.b] ? 1.f : 0.f;
+    case STPDE_RES_EQ: return v[in.a] == v[in.b] ? 1.f : 0.f;
+    case STPDE_RES_NE: return v[in.a] != v[in.b] ? 1.f : 0.f;
+    case STPDE_RES_AND: return (v[in.a] != 0.f && v[in.b] != 0.f) ? 1.f : 0.f;
+    case STPDE_RES_OR: return (v[in.a] != 0.f || v[in.b] != 0.f) ? 1.f : 0.f;
+    case STPDE_RES_NOT: return v[in.a] != 0.f ? 0.f : 1.f;
+    case STPDE_RES_SEL: return v[in.a] != 0.f ? v[STPDE_RES_SEL_THEN(in.b)] : v[STPDE_RES_SEL_ELSE(in.b)];
+    case STPDE_RES_STEPC: { const float x = v[in.a]; return x > 0.f ? 1.f : (x < 0.f ? 0.f : (x == 0.f ? in.c : x)); }
     default: return v[in.a];
   }
 }
@@ -146,7 +156,14 @@ __device__ __forceinline__ void res_bwd_ext(const stpde_res_ins& in, int i, cons
       g[in.b] += x > y ? 0.f : h;
       break;
     }
-    default: break;   // SIGN, STEP: adjoint 0
+    case STPDE_RES_SEL: {    // torch.where: the selected operand takes the cotangent, the other exactly +0 -- a select, not
+      // gi * mask: a NaN cotangent does not leak into the branch not taken -- and nothing goes into the mask
+      const bool then = v[in.a] != 0.f;
+      g[STPDE_RES_SEL_THEN(in.b)] += then ? gi : 0.f;
+      g[STPDE_RES_SEL_ELSE(in.b)] += then ? 0.f : gi;
+      break;
+    }
+    default: break;   // SIGN, STEP, STEPC, the comparisons and AND OR NOT: adjoint 0
   }
 }
 

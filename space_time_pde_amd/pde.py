@@ -20,6 +20,9 @@ Functions (beyond the reference's lambdify defaults): Max / Min of any arity, si
 (``dif(Abs(f), x)`` = sign(f) f_x), real and expression powers, tan sinh cosh asin acos atan atan2 evaluate elementwise on tensors
 on every strategy with torch's conventions (ties halve the cotangent, NaN propagates, sign' = H' = 0), and compile into the device
 residual program (``_compile_residual_program(..., extended=True)``, opcodes ``_RES_OPS_EXT``); DESIGN section 9 has the envelope.
+So do ``Piecewise`` with conditions made of the six relationals, ``And`` / ``Or`` / ``Not`` (a chain of torch.where: every branch
+is evaluated, the selected one takes the cotangent, the others exactly 0, nothing reaches a condition; NaN where no condition
+holds), ``Heaviside(a, h0)`` and the constants pi, E, EulerGamma, GoldenRatio, Catalan (opcodes ``_RES_OPS_COND``, compiled with ``extended=True, conditional=True``, which PDELayer passes).
 
 Coefficients (an extension of the reference surface): ``PDELayer(in_vars, out_vars, param_vars='nu')`` declares symbols whose
 values are tensors handed over with ``update_parameters`` -- one value for all points or one per batch element, optionally
@@ -89,20 +92,76 @@ def _t_atan2(a, b):
     return torch.atan2(*_tensor_args([a, b]))
 
 
+def _t_rel(op):
+    """A relational as a bool tensor: IEEE comparisons, a NaN operand gives False except for ``!=``."""
+    def rel(a, b):
+        return op(*_tensor_args([a, b]))
+    return rel
+
+
+def _t_and(*args):
+    r = args[0]
+    for a in args[1:]:
+        r = torch.logical_and(torch.as_tensor(r), torch.as_tensor(a))
+    return r
+
+
+def _t_or(*args):
+    r = args[0]
+    for a in args[1:]:
+        r = torch.logical_or(torch.as_tensor(r), torch.as_tensor(a))
+    return r
+
+
+def _t_not(a):
+    return torch.logical_not(torch.as_tensor(a))
+
+
+def _t_piecewise(like, *pairs):
+    """``Piecewise((e1, c1), ..., (en, cn))``: the right-nested torch.where(c1, e1, where(c2, e2, ...)).  Every branch is evaluated;
+    the selected one takes the cotangent and the others exactly 0 (torch.where's autograd).  A condition that is the constant
+    True ends the chain; without one the chain ends in NaN, sympy's value where no condition holds.  Branches that are plain
+    numbers become 0-d tensors of the dtype and device of ``like`` (a symbol of the expression) and broadcast."""
+    def val(e):
+        return e if torch.is_tensor(e) else torch.as_tensor(float(e), dtype=like.dtype, device=like.device)
+
+    chain, r = [], None
+    for e, c in pairs:
+        if c is True:
+            r = val(e)
+            break
+        if c is not False:
+            chain.append((val(e), c))
+    if r is None:
+        r = val(float("nan"))
+    for e, c in reversed(chain):
+        r = torch.where(c, e, r)
+    return r
+
+
 _TORCH_FUNCS = {"sin": torch.sin, "cos": torch.cos, "tan": torch.tan, "exp": torch.exp, "log": torch.log,
                 "sqrt": torch.sqrt, "tanh": torch.tanh, "sinh": torch.sinh, "cosh": torch.cosh, "Abs": torch.abs,
                 "asin": torch.asin, "acos": torch.acos, "atan": torch.atan, "atan2": _t_atan2, "Max": _t_max, "Min": _t_min,
-                "sign": _t_sign, "Heaviside": _t_heaviside}
+                "sign": _t_sign, "Heaviside": _t_heaviside, "Piecewise": _t_piecewise, "And": _t_and, "Or": _t_or, "Not": _t_not,
+                "StrictLessThan": _t_rel(torch.lt), "LessThan": _t_rel(torch.le), "StrictGreaterThan": _t_rel(torch.gt),
+                "GreaterThan": _t_rel(torch.ge), "Equality": _t_rel(torch.eq), "Unequality": _t_rel(torch.ne)}
 
 
 class _TorchPrinter(PythonCodePrinter):
-    """The printer sympy.lambdify picks for these modules, except that Max, Min, sign and Heaviside print as calls of the
-    elementwise functions above: as Python conditionals (the stock printer) they cannot take tensors."""
+    """The printer sympy.lambdify picks for these modules, except that Max, Min, sign, Heaviside, Piecewise, And / Or / Not and
+    the six relationals print as calls of the elementwise functions above: as Python conditionals and comparisons chained with
+    ``and`` / ``or`` (the stock printer) they cannot take tensors."""
 
     def _call(self, e):
         return "%s(%s)" % (e.func.__name__, ", ".join(self._print(a) for a in e.args))
 
-    _print_Max = _print_Min = _print_sign = _print_Heaviside = _call
+    _print_Max = _print_Min = _print_sign = _print_Heaviside = _print_And = _print_Or = _print_Not = _call
+    _print_Relational = _call
+
+    def _print_Piecewise(self, e):
+        like = min(e.free_symbols, key=lambda s: (s.name, getattr(s, "dummy_index", 0)))
+        pairs = ", ".join("(%s, %s)" % (self._print(v), self._print(c)) for v, c in e.args)
+        return "Piecewise(%s, %s)" % (self._print(like), pairs)
 
 
 def _lambdify(args, expr, extra=None):
@@ -150,7 +209,14 @@ _RES_OPS_EXT = {"TAN": 17, "SINH": 18, "COSH": 19, "ASIN": 20, "ACOS": 21, "ATAN
                 "MIN": 26, "MAX": 27, "SIGN": 28, "STEP": 29}
 _RES_UNARY_EXT = {sympy.tan: "TAN", sympy.sinh: "SINH", sympy.cosh: "COSH", sympy.asin: "ASIN", sympy.acos: "ACOS",
                   sympy.atan: "ATAN", sympy.sign: "SIGN"}
-_RES_OPS_ALL = dict(_RES_OPS, **_RES_OPS_EXT)
+# appended after STEP; only programs compiled with extended=True, conditional=True hold them: masks (1.0 / 0.0) of relationals
+# and logic, the three-operand select of a Piecewise chain -- a = mask, b = then | else << 16 (include/stpde_hip.h) -- and
+# Heaviside with H(0) = c
+_RES_OPS_COND = {"LT": 30, "LE": 31, "EQ": 32, "NE": 33, "AND": 34, "OR": 35, "NOT": 36, "SEL": 37, "STEPC": 38}
+_RES_REL = {sympy.StrictLessThan: ("LT", False), sympy.LessThan: ("LE", False), sympy.StrictGreaterThan: ("LT", True),
+            sympy.GreaterThan: ("LE", True), sympy.Equality: ("EQ", False), sympy.Unequality: ("NE", False)}   # (opcode, swap)
+_RES_NUMBER_SYMBOLS = (sympy.pi, sympy.E, sympy.EulerGamma, sympy.GoldenRatio, sympy.Catalan)
+_RES_OPS_ALL = dict(_RES_OPS, **_RES_OPS_EXT, **_RES_OPS_COND)
 _RES_MAX_INS = 192      # STPDE_RES_MAX_INS
 _RES_DT = np.dtype([("op", "<i4"), ("a", "<i4"), ("b", "<i4"), ("c", "<f4")])   # = stpde_res_ins
 
@@ -159,21 +225,59 @@ class _Unsupported(Exception):
     pass
 
 
-def _compile_residual_program(exprs, in_vars, sym_to_slot, extended=False):
+def _compile_residual_program(exprs, in_vars, sym_to_slot, extended=False, conditional=False):
     """Straight-line SSA program (common sub-expressions shared) for a list of sympy expressions.
 
     sym_to_slot: {sympy symbol: (stream, channel)} for the jet atoms.  Returns (numpy program, uses_x) or None when
     an expression contains something the device evaluator does not implement.  extended: also use the opcodes of
     _RES_OPS_EXT, for what the 17 of _RES_OPS cannot express (Max / Min as a chain, sign, Heaviside with H(0) = 1/2, real
-    and expression exponents, tan sinh cosh asin acos atan atan2); what compiles without them compiles to the same bytes."""
+    and expression exponents, tan sinh cosh asin acos atan atan2).  conditional (with extended): also use those of _RES_OPS_COND,
+    for what extended alone rejects (Piecewise over relationals joined by And / Or / Not as a chain of selects on float masks;
+    Heaviside with another H(0); pi, E, EulerGamma, GoldenRatio and Catalan as fp32 constants, as an exponent too).  What
+    compiles without a switch compiles to the same bytes with it."""
     ins, memo, uses_x = [], {}, [False]
 
     def emit(op, a=0, b=0, c=0.0):
         ins.append((_RES_OPS_ALL[op], int(a), int(b), float(c)))
         return len(ins) - 1
 
+    def number_symbol(e):
+        return float(np.float32(float(e.evalf(30))))
+
+    def cond(c):
+        """A Piecewise condition as a float mask, 1.0 or 0.0."""
+        if c in memo:
+            return memo[c]
+        if type(c) in _RES_REL:
+            op, swap = _RES_REL[type(c)]
+            a, b = rec(c.args[0]), rec(c.args[1])
+            idx = emit(op, b, a) if swap else emit(op, a, b)
+        elif isinstance(c, (sympy.And, sympy.Or)):
+            op = "AND" if isinstance(c, sympy.And) else "OR"
+            idx = cond(c.args[0])
+            for t in c.args[1:]:
+                idx = emit(op, idx, cond(t))
+        elif isinstance(c, sympy.Not):
+            idx = emit("NOT", cond(c.args[0]))
+        else:
+            raise _Unsupported(c)
+        memo[c] = idx
+        return idx
+
     def rec_ext(e):
         """What only the extended opcodes express."""
+        if conditional and e in _RES_NUMBER_SYMBOLS:
+            return emit("CONST", c=number_symbol(e))
+        if conditional and e.is_Piecewise:
+            # SEL(mask, then, else) from the last branch backwards; every branch is evaluated, as torch.where's are
+            pairs = list(e.args)
+            if pairs[-1][1] == sympy.true:
+                idx = rec(pairs.pop()[0])
+            else:
+                idx = emit("CONST", c=float("nan"))                 # no condition holds: sympy's nan
+            for ex, c in reversed(pairs):
+                idx = emit("SEL", cond(c), rec(ex) | idx << 16)
+            return idx
         if e.is_Pow:
             base, ex = e.args
             if ex.is_Float and float(ex).is_integer():
@@ -182,6 +286,8 @@ def _compile_residual_program(exprs, in_vars, sym_to_slot, extended=False):
                 if not (ex.is_real and ex.is_finite):
                     raise _Unsupported(e)
                 return emit("POWC", rec(base), c=float(ex))
+            if conditional and ex in _RES_NUMBER_SYMBOLS:
+                return emit("POWC", rec(base), c=number_symbol(ex))
             return emit("POW", rec(base), rec(ex))
         if e.func in (sympy.Max, sympy.Min):
             op = "MAX" if e.func is sympy.Max else "MIN"
@@ -191,6 +297,8 @@ def _compile_residual_program(exprs, in_vars, sym_to_slot, extended=False):
             return idx
         if e.func is sympy.Heaviside and (len(e.args) == 1 or e.args[1] == sympy.Rational(1, 2)):
             return emit("STEP", rec(e.args[0]))
+        if conditional and e.func is sympy.Heaviside and e.args[1].is_Number and e.args[1].is_real and e.args[1].is_finite:
+            return emit("STEPC", rec(e.args[0]), c=float(e.args[1]))    # (STEP's c is 0 and means 1/2)
         if e.func is sympy.atan2:
             return emit("ATAN2", rec(e.args[0]), rec(e.args[1]))
         if e.func in _RES_UNARY_EXT and len(e.args) == 1:
@@ -388,6 +496,9 @@ class PDELayer(object):
             groups = {}
             for name, prog in progs.items():
                 s2 = {k: v for k, v in prog.syms.items() if len(k[1]) == 2}
+                # a Piecewise condition is not differentiated below: a second derivative in one is not linear use
+                if s2 and any(c.has(*s2.values()) for pw in prog.expr.atoms(sympy.Piecewise) for _, c in pw.args):
+                    return None
                 for key, sym in s2.items():
                     coeff = sympy.diff(prog.expr, sym)
                     if any(coeff.has(t) for t in s2.values()):
@@ -606,7 +717,8 @@ class PDELayer(object):
             for prog in progs.values():
                 for akey, sym in prog.syms.items():
                     slots[sym] = (stream_of[akey[1]], akey[0])
-            comp = _compile_residual_program([p.expr for p in progs.values()], list(self.in_vars), slots, extended=True)
+            comp = _compile_residual_program([p.expr for p in progs.values()], list(self.in_vars), slots, extended=True,
+                                             conditional=True)
             ent = None
             if comp is not None:
                 arr, uses_x = comp

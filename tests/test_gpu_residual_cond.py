@@ -1,0 +1,293 @@
+"""The opcodes appended to the residual evaluator after STEP (LT LE EQ NE AND OR NOT SEL STEPC: Piecewise with relational conditions,
+Heaviside(a, h0)) on the device, against tests/residual_cond_model.py (whose rules tests/test_residual_cond_host.py checks against
+torch's autograd), the way tests/test_gpu_residual_ext.py holds the thirteen before them.
+
+* Every new opcode is comparisons and selects: values and adjoints BIT-EQUAL to the float32 model on 4096 normal-range rows, 64 of
+  them tied, and on every combination of 0, -0, 1, -1, +-Inf, NaN, with NaN and infinite cotangents on either side of a select.
+* One program with all of them at point counts around the 256-thread block, dense and as a slice of padded rows.
+* End to end, dim = 3 and (t, x): equations that are discontinuous across their switch, through query_local_implicit_grid and
+  PDELayer, against the fp64 CPU evaluation of the same layer with the tolerances of tests/test_gpu_residual_ext.py and
+  tests/test_gpu_lig_nd_jet_backward.py.  A point whose condition is nearly tied may take the other branch in fp32, which is an
+  error of neither evaluation, so the points are chosen by the fp64 reference alone: of the seeded candidates those whose
+  condition has its two sides closer than 1e-3 in fp64 are dropped (at most a tenth of them may be) and the first of the rest kept.
+
+NaN / Inf here are DATA fed to element-wise kernels: ordinary arithmetic, every index in bounds (residual_cond_model.program
+checks the operands of the hand-written programs)."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+from tests import residual_cond_model as C
+from tests import residual_model as M
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+F = np.float32
+MARGIN = 1e-3
+_cache = {}
+
+
+def _n_eq(prog):
+    return int((prog["op"] == C.OPS["OUT"]).sum())
+
+
+def _apply(prog, jets_t, x=None):
+    from space_time_pde_amd import pde
+    prog_t = torch.from_numpy(prog.view(np.uint8).copy()).to(DEV)          # as PDELayer._residues_hip
+    x2d = None if x is None else torch.from_numpy(np.array(x, dtype=F)).to(DEV)
+    return pde._ResidualHip.apply(jets_t, x2d, prog_t, len(prog), _n_eq(prog))
+
+
+def _device(prog, jets, res_bar, x=None):
+    jets_t = torch.from_numpy(np.array(jets, dtype=F)).to(DEV).requires_grad_(True)
+    res = _apply(prog, jets_t, x)
+    res.backward(torch.from_numpy(np.array(res_bar, dtype=F)).to(DEV))
+    torch.cuda.synchronize()
+    return res.detach().cpu().numpy(), jets_t.grad.cpu().numpy()
+
+
+def _assert_bits(got, want, what):
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    assert M.same_bits(got, want).all(), "%s: %s" % (what, M.bit_mismatches(got, want))
+
+
+# ---- opcode level -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", C.EXACT_CASES)
+def test_new_opcode_is_bit_equal_to_the_fp32_model(hiplib, name):
+    prog, jets, res_bar = C.exact_case(name)
+    res, bar = _device(prog, jets, res_bar)
+    _assert_bits(res, np.stack(C.run(prog, jets, None, F)), name + " values")
+    _assert_bits(bar, C.adjoint(prog, jets, None, res_bar, F), name + " adjoint")
+    if name == "SEL":       # literally: under a NaN / infinite cotangent the operand not taken by a < b ? a : b stays finite
+        a, b = jets[0, 0], jets[0, 1]
+        rows = ~np.isfinite(res_bar[0]) & (a < b) & np.isfinite(a) & np.isfinite(res_bar[1])
+        assert rows.sum() > 100 and np.isfinite(bar[0, 1][rows]).all()
+
+
+@pytest.mark.parametrize("pad", [0, 3])
+@pytest.mark.parametrize("P", [1, 255, 256, 257])
+def test_point_counts_and_sliced_jets(hiplib, P, pad):
+    """pad = 0: dense jets, bit-equal to the float32 model (the program holds exact opcodes only).  pad = 3: jets = buf[:, :, :P]
+    of a leaf buf whose padding holds NaN -- values and gradient bit-equal again, the padding's gradient exactly +0."""
+    c = C.mixed_case()
+    prog, jets, x, cot = c["prog"], np.ascontiguousarray(c["jets"][:, :, :P]), c["x"][:P], np.ascontiguousarray(c["cot"][:, :P])
+    want_res, want_bar = np.stack(C.run(prog, jets, x, F)), C.adjoint(prog, jets, x, cot, F)
+    if pad == 0:
+        res, bar = _device(prog, jets, cot, x)
+        _assert_bits(res, want_res, "values")
+        _assert_bits(bar, want_bar, "adjoint")
+        return
+    buf = torch.full((1, 2, P + pad), float("nan"))
+    buf[:, :, :P] = torch.from_numpy(np.array(jets))
+    buf = buf.to(DEV).requires_grad_(True)
+    view = buf[:, :, :P]
+    assert view.stride() == ((P + pad) * 2, P + pad, 1)
+    res = _apply(prog, view, x)
+    res.backward(torch.from_numpy(np.array(cot)).to(DEV))
+    torch.cuda.synchronize()
+    _assert_bits(res.detach().cpu().numpy(), want_res, "values of the sliced jets")
+    grad = buf.grad.cpu().numpy()
+    _assert_bits(np.ascontiguousarray(grad[:, :, :P]), want_bar, "gradient of the sliced jets")
+    assert not grad[:, :, P:].view(np.int32).any(), "the padding of the gradient is not +0"
+
+
+# ---- end to end, dim = 3 ------------------------------------------------------------------------------------------------------------
+SWITCHED = {
+    "switched_u": "dif(u,t) + Piecewise((u*dif(u,x), u > 0), (2*u*dif(u,z), True)) - 0.01*dif(dif(u,x),x)",
+    "banded_w": "dif(w,t) + Piecewise((w, (x > 0.25) & (x < 0.5)), (sin(pi*x)*dif(w,x), True))",
+}
+N_CAND, N_PTS = 512, 257
+
+
+def _relerr(a, b):
+    a, b = a.detach().cpu().double(), b.detach().cpu().double()
+    return (a - b).abs().max().item() / b.abs().max().item()
+
+
+def _keep_first(far, n):
+    """far [B, N] bool -> indices [B, n] of the first n candidates of every batch element that are far from every tie."""
+    dropped = (~far).sum().item()
+    assert dropped <= 0.10 * far.numel(), "%d of %d candidates are within %g of a tie" % (dropped, far.numel(), MARGIN)
+    idx = []
+    for b in range(far.shape[0]):
+        k = torch.nonzero(far[b]).reshape(-1)
+        assert len(k) >= n
+        idx.append(k[:n])
+    return torch.stack(idx), dropped
+
+
+def _make_switched():
+    from space_time_pde_amd import pde
+    layer = pde.PDELayer("t, z, x", "u, w")
+    for k, e in SWITCHED.items():
+        layer.add_equation(e, k)
+    return layer
+
+
+def _dim3_case():
+    """The fixture of tests/test_gpu_residual_ext.py's end-to-end test (latent [2, 4, 4, 4, 8], ImNet(nf = 16, softplus), seeds 21
+    and 5) with 257 of 512 candidate points chosen by the fp64 reference, and that reference: the same PDELayer on the CPU in fp64,
+    reverse-sweep strategy, over the oracle's local-implicit-grid query.  Built once, never modified."""
+    if "dim3" in _cache:
+        return _cache["dim3"]
+    from oracle import cpu_ref as O
+    from space_time_pde_amd import implicit_net
+    g = torch.Generator().manual_seed(21)
+    lat0 = 0.5 * torch.randn(2, 4, 4, 4, 8, generator=g)
+    cand = 0.02 + 0.96 * torch.rand(2, N_CAND, 3, generator=g)
+    cot_y = torch.randn(2, N_PTS, 2, generator=g)
+    cot_r = {k: torch.randn(2, N_PTS, 1, generator=g) for k in SWITCHED}
+    torch.manual_seed(5)
+    net = implicit_net.ImNet(dim=3, in_features=8, out_features=2, nf=16, activation=torch.nn.Softplus)
+    p64 = [(net.fc[k].weight.detach().double().requires_grad_(True), net.fc[k].bias.detach().double().requires_grad_(True))
+           for k in range(6)]
+    lat64 = lat0.double().requires_grad_(True)
+    act = O.activation_fn("softplus")
+
+    def query(q):
+        return O.query_lig(lambda x: O.imnet_forward(p64, x, act), lat64, q, 0., 1.)
+
+    with torch.no_grad():
+        u = query(cand.double())[..., 0]
+    xc = cand.double()[..., 2]
+    far = (u.abs() >= MARGIN) & ((xc - 0.25).abs() >= MARGIN) & ((xc - 0.5).abs() >= MARGIN)
+    idx, dropped = _keep_first(far, N_PTS)
+    pts = torch.gather(cand, 1, idx.unsqueeze(-1).expand(-1, -1, 3)).contiguous()
+    ref_layer = _make_switched()
+    ref_layer.update_forward_method(query)
+    y64, r64 = ref_layer(pts.double().clone())
+    f64 = (y64 * cot_y.double()).sum() + sum((r64[k] * cot_r[k].double()).sum() for k in cot_r)
+    f64.backward()
+    u64, x64 = y64[..., 0].detach(), pts.double()[..., 2]
+    band = (x64 > 0.25) & (x64 < 0.5)
+    print("dim 3: %d of %d candidates dropped; u in [%.3f, %.3f], u > 0 at %.0f %% of the points, %.0f %% in the band"
+          % (dropped, far.numel(), u64.min(), u64.max(), 100 * (u64 > 0).double().mean(), 100 * band.double().mean()))
+    assert 0.2 < (u64 > 0).double().mean() < 0.8 and 0.1 < band.double().mean() < 0.9      # every branch is taken
+    _cache["dim3"] = dict(net=net, lat0=lat0, pts=pts, cot_y=cot_y, cot_r=cot_r, r64={k: v.detach() for k, v in r64.items()},
+                          f64=f64.item(), dlat=lat64.grad, grads=[(w.grad, b.grad) for w, b in p64])
+    return _cache["dim3"]
+
+
+@pytest.mark.parametrize("prec", ["fp32", "fp32x3"])
+def test_switched_system_matches_the_fp64_cpu_evaluation(hiplib, prec, monkeypatch):
+    """Tolerances of test_upwinded_power_law_system_matches_the_fp64_cpu_evaluation: residuals 3e-5 of their maximum, the
+    functional 2e-4 and every gradient 3e-4 of its maximum."""
+    from space_time_pde_amd import _lib, lig_jet, local_implicit_grid as lig
+    monkeypatch.setattr(lig_jet, "mlp_precision", prec)
+    c = _dim3_case()
+    net = copy.deepcopy(c["net"]).to(DEV)
+    cot_y, cot_r = c["cot_y"], c["cot_r"]
+    layer = _make_switched()
+    lat = c["lat0"].to(DEV).requires_grad_(True)
+    layer.update_forward_method(lambda q: lig.query_local_implicit_grid(net, lat, q, 0., 1.))
+    n0, f0 = lig.stats["hip_jet_calls"], lig.stats.get("residual_torch_fallbacks", 0)
+    with _lib.dispatch_trace() as tr:
+        pred, res = layer(c["pts"].to(DEV))
+        f = (pred * cot_y.to(DEV)).sum() + sum((res[k] * cot_r[k].to(DEV)).sum() for k in cot_r)
+        f.backward()
+        torch.cuda.synchronize()
+    assert lig.stats["hip_jet_calls"] == n0 + 1, "HIP jet path was not taken"
+    assert lig.stats.get("residual_torch_fallbacks", 0) == f0
+    assert tr.has("k_residual_fwd") and tr.has("k_residual_bwd"), "\n".join(tr.kernels)
+    prog_t, nins, _ = next(iter(layer._res_progs.values()))
+    ops = set(np.frombuffer(prog_t.cpu().numpy().tobytes(), dtype=M.DT)["op"].tolist())
+    assert {C.OPS["LT"], C.OPS["AND"], C.OPS["SEL"]} <= ops
+    for k in SWITCHED:
+        want = c["r64"][k]
+        err = (res[k].detach().cpu().double() - want).abs().max().item()
+        print("%s %s: residual max err %.3e of max %.3e" % (prec, k, err, want.abs().max().item()))
+        assert err < 3e-5 * want.abs().max().item(), k
+    print("%s: functional %.9g against %.9g" % (prec, f.item(), c["f64"]))
+    assert abs(f.item() - c["f64"]) < 2e-4 * abs(c["f64"])
+    errs = {"dlat": _relerr(lat.grad, c["dlat"])}
+    for k in range(6):
+        errs["dW%d" % k] = _relerr(net.fc[k].weight.grad, c["grads"][k][0])
+        errs["db%d" % k] = _relerr(net.fc[k].bias.grad, c["grads"][k][1])
+    print(prec, " ".join("%s %.2e" % kv for kv in errs.items()))
+    for k, v in errs.items():
+        assert v < 3e-4, (k, v)
+
+
+# ---- end to end, (t, x) -----------------------------------------------------------------------------------------------------------
+ONE_SIDED = "dif(u,t) + Piecewise((u, u > 0), (0, True))*dif(u,x) - 0.01*dif(dif(u,x),x)"
+TOL_GRAD = 2e-4          # tests/test_gpu_lig_nd_jet_backward.py: the loss, d latent and the 12 parameter gradients
+ND_CAND, ND_PTS = 64, 37
+
+
+@pytest.fixture
+def train(hiplib):
+    from space_time_pde_amd import lig_jet
+    prev = lig_jet.set_nd_jets(True), lig_jet.set_nd_jet_backward(True)
+    yield lig_jet
+    lig_jet.set_nd_jets(prev[0])
+    lig_jet.set_nd_jet_backward(prev[1])
+
+
+def _tx_case():
+    """The (4, 5) grid, c = 8, softplus IM-NET and the loss of tests/test_gpu_lig_nd_jet_backward.py::test_pde_layer_training_step
+    (a regression loss on the value plus an l2 residual loss); 37 of 64 seeded candidate points per batch element chosen by the
+    fp64 reference (oracle jets -> the equation as a torch.where -> autograd).  Built once, never modified."""
+    if "tx" in _cache:
+        return _cache["tx"]
+    from oracle import jet_ref as J
+    from tests import lig_nd_jet_bwd_model as BM
+    lat, _, _ = BM.make_case(2, (4, 5), 8)
+    net = BM.make_net(2, 8, "softplus", 1)
+    g = torch.Generator().manual_seed(31)
+    cand = 0.02 + 0.96 * torch.rand(2, ND_CAND, 2, generator=g)
+    tgt = torch.randn(2, ND_PTS, 1, generator=g)
+    prm = [t.detach().double().requires_grad_(True) for k in range(6) for t in (net.fc[k].weight, net.fc[k].bias)]
+    latd = lat.double().requires_grad_(True)
+    pp = [(1, 1), (1, 1)]
+
+    def jets_of(p):
+        return BM.to_hip_order(J.lig_jets(list(zip(prm[0::2], prm[1::2])), "softplus", latd, p.double(), 0., 1., second=pp), 2)
+
+    with torch.no_grad():
+        # this net's u has one sign on the whole grid: move its output bias to the median of u, so that the switch is exercised
+        shift = jets_of(cand)[0][0].median().item()
+        net.fc[5].bias -= shift
+        prm[11].copy_(net.fc[5].bias.double())
+        u = jets_of(cand)[0][0].reshape(2, ND_CAND)
+    idx, dropped = _keep_first(u.abs() >= MARGIN, ND_PTS)
+    pts = torch.gather(cand, 1, idx.unsqueeze(-1).expand(-1, -1, 2)).contiguous()
+    j = jets_of(pts)
+    u = j[0][0]
+    res = j[1][0] + torch.where(u > 0, u, torch.zeros_like(u)) * j[2][0] - 0.01 * j[4][0]
+    y = j[0].t().reshape(2, ND_PTS, 1)
+    loss = ((y - tgt.double()) ** 2).sum() + (res ** 2).sum()
+    gr = torch.autograd.grad(loss, [latd] + prm)
+    frac = (u > 0).double().mean().item()
+    print("(t, x): %d of %d candidates dropped; u > 0 at %.0f %% of the points" % (dropped, 2 * ND_CAND, 100 * frac))
+    assert 0.15 < frac < 0.85
+    _cache["tx"] = dict(net=net, lat=lat, pts=pts, tgt=tgt, loss=loss.item(), res=res.detach(), dlat=gr[0], grads=list(gr[1:]))
+    return _cache["tx"]
+
+
+def test_one_sided_advection_trains_on_a_2d_grid(train):
+    from space_time_pde_amd import _lib, local_implicit_grid as lig, pde
+    c = _tx_case()
+    layer = pde.PDELayer("t, x", "u")
+    layer.add_equation(ONE_SIDED, "one_sided")
+    net = copy.deepcopy(c["net"]).to(DEV)
+    latd, ptsd = c["lat"].to(DEV).requires_grad_(True), c["pts"].to(DEV)
+    layer.update_forward_method(lambda q: lig.query_local_implicit_grid(net, latd, q, 0., 1.))
+    h0, g0, f0 = lig.stats["hip_jet_calls"], lig.stats["generic_calls"], lig.stats.get("residual_torch_fallbacks", 0)
+    with _lib.dispatch_trace() as tr:
+        y, res = layer(ptsd, return_residue=True)
+        loss = ((y - c["tgt"].to(DEV)) ** 2).sum() + (res["one_sided"] ** 2).sum()
+        loss.backward()
+        torch.cuda.synchronize()
+    assert lig.stats["hip_jet_calls"] == h0 + 1 and lig.stats["generic_calls"] == g0
+    assert lig.stats.get("residual_torch_fallbacks", 0) == f0
+    assert tr.has("k_reduce_nd_jet_bwd<", "D = 2") and tr.has("k_residual_fwd") and tr.has("k_residual_bwd"), tr.kernels
+    prog_t, nins, _ = next(iter(layer._res_progs.values()))
+    ops = set(np.frombuffer(prog_t.cpu().numpy().tobytes(), dtype=M.DT)["op"].tolist())
+    assert {C.OPS["LT"], C.OPS["SEL"]} <= ops
+    grads = [t.grad for k in range(6) for t in (net.fc[k].weight, net.fc[k].bias)]
+    err = {"loss": abs(loss.item() - c["loss"]) / abs(c["loss"]), "residual": _relerr(res["one_sided"].reshape(-1), c["res"]),
+           "dlatent": _relerr(latd.grad, c["dlat"]), "dW": max(_relerr(g, r) for g, r in zip(grads, c["grads"]))}
+    print("one-sided advection step", err)
+    assert err["loss"] < TOL_GRAD and err["dlatent"] < TOL_GRAD and err["dW"] < TOL_GRAD, err       # (the residual: printed only)

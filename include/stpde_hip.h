@@ -676,10 +676,8 @@ enum {
   STPDE_RES_NEG, STPDE_RES_POWI, STPDE_RES_SIN, STPDE_RES_COS, STPDE_RES_EXP, STPDE_RES_LOG, STPDE_RES_SQRT,
   STPDE_RES_TANH, STPDE_RES_ABS, STPDE_RES_OUT,
   STPDE_RES_TAN, STPDE_RES_SINH, STPDE_RES_COSH, STPDE_RES_ASIN, STPDE_RES_ACOS, STPDE_RES_ATAN, STPDE_RES_ATAN2,
-  STPDE_RES_POWC, STPDE_RES_POW, STPDE_RES_MIN, STPDE_RES_MAX, STPDE_RES_SIGN, STPDE_RES_STEP
-};
-enum { /* continues the list above */
-  STPDE_RES_LT = STPDE_RES_STEP + 1, STPDE_RES_LE, STPDE_RES_EQ, STPDE_RES_NE, STPDE_RES_AND, STPDE_RES_OR, STPDE_RES_NOT,
+  STPDE_RES_POWC, STPDE_RES_POW, STPDE_RES_MIN, STPDE_RES_MAX, STPDE_RES_SIGN, STPDE_RES_STEP,
+  STPDE_RES_LT, STPDE_RES_LE, STPDE_RES_EQ, STPDE_RES_NE, STPDE_RES_AND, STPDE_RES_OR, STPDE_RES_NOT,
   STPDE_RES_SEL, STPDE_RES_STEPC
 };
 #define STPDE_RES_SEL_THEN(b) ((int)((unsigned)(b) & 0xffffu))

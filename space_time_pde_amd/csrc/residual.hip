@@ -19,22 +19,26 @@ struct ResArgs {
   float* jets_bar;             // same layout as jets, zero-filled by the caller
 };
 
-// x^c for a real constant c = n + f, n = trunc(c): the integer part by POWI's own square-and-multiply (and 1 / r for n < 0), the
-// fraction through powf.  An integral c -- c = 1, or the c - 1 = 0 of its adjoint -- then costs no rounding of the math library
-// (its powf(x, 1) is not x in every bit), and the result keeps pow's conventions: NaN for x < 0 unless f = 0, the sign of x for an
-// odd integral c, +0 / +Inf at x = -0 otherwise (hence |x| under the integer part when f != 0).
-__device__ __forceinline__ float res_powc(float x, float c) {
-  const float n = truncf(c), f = c - n;
-  if (fabsf(n) > 64.f) return powf(x, c);
-  float base = f != 0.f ? fabsf(x) : x, r = 1.f;
-  const int ni = (int)n;
-  int e = ni < 0 ? -ni : ni;
+// base^n for an integer n: square-and-multiply on |n|, then 1 / r for n < 0.  POWI's value, the x^(n-1) of its adjoint and the
+// integer part of POWC all take it, so the three stay the same sequence of IEEE multiplications.
+__device__ __forceinline__ float res_ipow(float base, int n) {
+  float r = 1.f;
+  int e = n < 0 ? -n : n;
   while (e) {
     if (e & 1) r *= base;
     base *= base;
     e >>= 1;
   }
-  if (ni < 0) r = 1.f / r;
+  return n < 0 ? 1.f / r : r;
+}
+
+// x^c for a real constant c = n + f, n = trunc(c): the integer part by res_ipow, the fraction through powf.  An integral c -- c = 1, or the c - 1 = 0 of its adjoint -- then costs no rounding of the math library
+// (its powf(x, 1) is not x in every bit), and the result keeps pow's conventions: NaN for x < 0 unless f = 0, the sign of x for an
+// odd integral c, +0 / +Inf at x = -0 otherwise (hence |x| under the integer part when f != 0).
+__device__ __forceinline__ float res_powc(float x, float c) {
+  const float n = truncf(c), f = c - n;
+  if (fabsf(n) > 64.f) return powf(x, c);
+  const float r = res_ipow(f != 0.f ? fabsf(x) : x, (int)n);
   return f != 0.f ? r * powf(x, f) : r;
 }
 
@@ -81,16 +85,7 @@ __device__ __forceinline__ float res_eval(const stpde_res_ins& in, const float* 
     case STPDE_RES_MUL: return v[in.a] * v[in.b];
     case STPDE_RES_DIV: return v[in.a] / v[in.b];
     case STPDE_RES_NEG: return -v[in.a];
-    case STPDE_RES_POWI: {
-      float base = v[in.a], r = 1.f;
-      int e = in.b < 0 ? -in.b : in.b;
-      while (e) {
-        if (e & 1) r *= base;
-        base *= base;
-        e >>= 1;
-      }
-      return in.b < 0 ? 1.f / r : r;
-    }
+    case STPDE_RES_POWI: return res_ipow(v[in.a], in.b);
     case STPDE_RES_SIN: return sinf(v[in.a]);
     case STPDE_RES_COS: return cosf(v[in.a]);
     case STPDE_RES_EXP: return expf(v[in.a]);
@@ -197,20 +192,9 @@ __global__ __launch_bounds__(256) void k_residual_bwd(ResArgs a) {
       case STPDE_RES_MUL: g[in.a] += gi * v[in.b]; g[in.b] += gi * v[in.a]; break;
       case STPDE_RES_DIV: g[in.a] += gi / v[in.b]; g[in.b] -= gi * v[i] / v[in.b]; break;
       case STPDE_RES_NEG: g[in.a] -= gi; break;
-      case STPDE_RES_POWI: {   // d(x^n)/dx = n x^(n-1), evaluated without dividing by x (x = 0 is a regular point for n >= 1)
-        if (in.b != 0) {
-          const int m = in.b - 1;
-          float base = v[in.a], r = 1.f;
-          int e = m < 0 ? -m : m;
-          while (e) {
-            if (e & 1) r *= base;
-            base *= base;
-            e >>= 1;
-          }
-          g[in.a] += gi * (float)in.b * (m < 0 ? 1.f / r : r);
-        }
+      case STPDE_RES_POWI:   // d(x^n)/dx = n x^(n-1), evaluated without dividing by x (x = 0 is a regular point for n >= 1)
+        if (in.b != 0) g[in.a] += gi * (float)in.b * res_ipow(v[in.a], in.b - 1);
         break;
-      }
       case STPDE_RES_SIN: g[in.a] += gi * cosf(v[in.a]); break;
       case STPDE_RES_COS: g[in.a] -= gi * sinf(v[in.a]); break;
       case STPDE_RES_EXP: g[in.a] += gi * v[i]; break;

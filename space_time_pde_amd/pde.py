@@ -19,10 +19,12 @@ Two evaluation strategies:
 Functions (beyond the reference's lambdify defaults): Max / Min of any arity, sign, Heaviside (H(0) = 1/2), Abs under a ``dif``
 (``dif(Abs(f), x)`` = sign(f) f_x), real and expression powers, tan sinh cosh asin acos atan atan2 evaluate elementwise on tensors
 on every strategy with torch's conventions (ties halve the cotangent, NaN propagates, sign' = H' = 0), and compile into the device
-residual program (``_compile_residual_program(..., extended=True)``, opcodes ``_RES_OPS_EXT``); DESIGN section 9 has the envelope.
+residual program (``_compile_residual_program(..., extended=True)``, opcodes TAN .. STEP of the one table ``_RES_OPS``); DESIGN
+section 9 has the envelope.
 So do ``Piecewise`` with conditions made of the six relationals, ``And`` / ``Or`` / ``Not`` (a chain of torch.where: every branch
 is evaluated, the selected one takes the cotangent, the others exactly 0, nothing reaches a condition; NaN where no condition
-holds), ``Heaviside(a, h0)`` and the constants pi, E, EulerGamma, GoldenRatio, Catalan (opcodes ``_RES_OPS_COND``, compiled with ``extended=True, conditional=True``, which PDELayer passes).
+holds), ``Heaviside(a, h0)`` and the constants pi, E, EulerGamma, GoldenRatio, Catalan (opcodes LT .. STEPC of
+``_RES_OPS``, compiled with ``extended=True, conditional=True``, which PDELayer passes).
 
 Coefficients (an extension of the reference surface): ``PDELayer(in_vars, out_vars, param_vars='nu')`` declares symbols whose
 values are tensors handed over with ``update_parameters`` -- one value for all points or one per batch element, optionally
@@ -200,23 +202,21 @@ class _JetProgram:
 
 
 # ---- residual programs for the HIP evaluator (stpde_residual_fwd / _bwd) ---------------------------------------
-_RES_OPS = {"JET": 0, "X": 1, "CONST": 2, "ADD": 3, "SUB": 4, "MUL": 5, "DIV": 6, "NEG": 7, "POWI": 8, "SIN": 9, "COS": 10,
-            "EXP": 11, "LOG": 12, "SQRT": 13, "TANH": 14, "ABS": 15, "OUT": 16}
+# The opcodes, numbered in the order of the STPDE_RES_* enum of include/stpde_hip.h.  JET .. OUT are what every program may hold;
+# TAN .. STEP only programs compiled with extended=True; LT .. STEPC only those compiled with extended=True, conditional=True:
+# masks (1.0 / 0.0) of relationals and logic, the three-operand select of a Piecewise chain -- a = mask, b = then | else << 16 --
+# and Heaviside with H(0) = c.
+_RES_OPS = {name: k for k, name in enumerate(
+    "JET X CONST ADD SUB MUL DIV NEG POWI SIN COS EXP LOG SQRT TANH ABS OUT "
+    "TAN SINH COSH ASIN ACOS ATAN ATAN2 POWC POW MIN MAX SIGN STEP "
+    "LT LE EQ NE AND OR NOT SEL STEPC".split())}
 _RES_UNARY = {sympy.sin: "SIN", sympy.cos: "COS", sympy.exp: "EXP", sympy.log: "LOG", sympy.tanh: "TANH",
               sympy.Abs: "ABS"}
-# appended after OUT (include/stpde_hip.h); only programs compiled with extended=True hold them
-_RES_OPS_EXT = {"TAN": 17, "SINH": 18, "COSH": 19, "ASIN": 20, "ACOS": 21, "ATAN": 22, "ATAN2": 23, "POWC": 24, "POW": 25,
-                "MIN": 26, "MAX": 27, "SIGN": 28, "STEP": 29}
 _RES_UNARY_EXT = {sympy.tan: "TAN", sympy.sinh: "SINH", sympy.cosh: "COSH", sympy.asin: "ASIN", sympy.acos: "ACOS",
                   sympy.atan: "ATAN", sympy.sign: "SIGN"}
-# appended after STEP; only programs compiled with extended=True, conditional=True hold them: masks (1.0 / 0.0) of relationals
-# and logic, the three-operand select of a Piecewise chain -- a = mask, b = then | else << 16 (include/stpde_hip.h) -- and
-# Heaviside with H(0) = c
-_RES_OPS_COND = {"LT": 30, "LE": 31, "EQ": 32, "NE": 33, "AND": 34, "OR": 35, "NOT": 36, "SEL": 37, "STEPC": 38}
 _RES_REL = {sympy.StrictLessThan: ("LT", False), sympy.LessThan: ("LE", False), sympy.StrictGreaterThan: ("LT", True),
             sympy.GreaterThan: ("LE", True), sympy.Equality: ("EQ", False), sympy.Unequality: ("NE", False)}   # (opcode, swap)
 _RES_NUMBER_SYMBOLS = (sympy.pi, sympy.E, sympy.EulerGamma, sympy.GoldenRatio, sympy.Catalan)
-_RES_OPS_ALL = dict(_RES_OPS, **_RES_OPS_EXT, **_RES_OPS_COND)
 _RES_MAX_INS = 192      # STPDE_RES_MAX_INS
 _RES_DT = np.dtype([("op", "<i4"), ("a", "<i4"), ("b", "<i4"), ("c", "<f4")])   # = stpde_res_ins
 
@@ -229,16 +229,16 @@ def _compile_residual_program(exprs, in_vars, sym_to_slot, extended=False, condi
     """Straight-line SSA program (common sub-expressions shared) for a list of sympy expressions.
 
     sym_to_slot: {sympy symbol: (stream, channel)} for the jet atoms.  Returns (numpy program, uses_x) or None when
-    an expression contains something the device evaluator does not implement.  extended: also use the opcodes of
-    _RES_OPS_EXT, for what the 17 of _RES_OPS cannot express (Max / Min as a chain, sign, Heaviside with H(0) = 1/2, real
-    and expression exponents, tan sinh cosh asin acos atan atan2).  conditional (with extended): also use those of _RES_OPS_COND,
+    an expression contains something the device evaluator does not implement.  extended: also use the opcodes
+    TAN .. STEP of _RES_OPS, for what the 17 up to OUT cannot express (Max / Min as a chain, sign, Heaviside with H(0) = 1/2, real
+    and expression exponents, tan sinh cosh asin acos atan atan2).  conditional (with extended): also use LT .. STEPC,
     for what extended alone rejects (Piecewise over relationals joined by And / Or / Not as a chain of selects on float masks;
     Heaviside with another H(0); pi, E, EulerGamma, GoldenRatio and Catalan as fp32 constants, as an exponent too).  What
     compiles without a switch compiles to the same bytes with it."""
     ins, memo, uses_x = [], {}, [False]
 
     def emit(op, a=0, b=0, c=0.0):
-        ins.append((_RES_OPS_ALL[op], int(a), int(b), float(c)))
+        ins.append((_RES_OPS[op], int(a), int(b), float(c)))
         return len(ins) - 1
 
     def number_symbol(e):

@@ -1,5 +1,5 @@
 """The opcodes appended to the residual evaluator after STEP (LT LE EQ NE AND OR NOT SEL STEPC: Piecewise with relational conditions,
-Heaviside(a, h0)) on the device, against tests/residual_cond_model.py (whose rules tests/test_residual_cond_host.py checks against
+Heaviside(a, h0)) on the device, against tests/residual_model.py (whose rules tests/test_residual_cond_host.py checks against
 torch's autograd), the way tests/test_gpu_residual_ext.py holds the thirteen before them.
 
 * Every new opcode is comparisons and selects: values and adjoints BIT-EQUAL to the float32 model on 4096 normal-range rows, 64 of
@@ -11,7 +11,7 @@ torch's autograd), the way tests/test_gpu_residual_ext.py holds the thirteen bef
   error of neither evaluation, so the points are chosen by the fp64 reference alone: of the seeded candidates those whose
   condition has its two sides closer than 1e-3 in fp64 are dropped (at most a tenth of them may be) and the first of the rest kept.
 
-NaN / Inf here are DATA fed to element-wise kernels: ordinary arithmetic, every index in bounds (residual_cond_model.program
+NaN / Inf here are DATA fed to element-wise kernels: ordinary arithmetic, every index in bounds (residual_model.program
 checks the operands of the hand-written programs)."""
 import copy
 
@@ -19,7 +19,6 @@ import numpy as np
 import pytest
 import torch
 
-from tests import residual_cond_model as C
 from tests import residual_model as M
 
 pytestmark = pytest.mark.gpu
@@ -30,7 +29,7 @@ _cache = {}
 
 
 def _n_eq(prog):
-    return int((prog["op"] == C.OPS["OUT"]).sum())
+    return int((prog["op"] == M.OPS["OUT"]).sum())
 
 
 def _apply(prog, jets_t, x=None):
@@ -54,12 +53,12 @@ def _assert_bits(got, want, what):
 
 
 # ---- opcode level -----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", C.EXACT_CASES)
+@pytest.mark.parametrize("name", M.EXACT_CASES_COND)
 def test_new_opcode_is_bit_equal_to_the_fp32_model(hiplib, name):
-    prog, jets, res_bar = C.exact_case(name)
+    prog, jets, _, res_bar = M.exact_case(name)
     res, bar = _device(prog, jets, res_bar)
-    _assert_bits(res, np.stack(C.run(prog, jets, None, F)), name + " values")
-    _assert_bits(bar, C.adjoint(prog, jets, None, res_bar, F), name + " adjoint")
+    _assert_bits(res, np.stack(M.run(prog, jets, None, F)), name + " values")
+    _assert_bits(bar, M.adjoint(prog, jets, None, res_bar, F), name + " adjoint")
     if name == "SEL":       # literally: under a NaN / infinite cotangent the operand not taken by a < b ? a : b stays finite
         a, b = jets[0, 0], jets[0, 1]
         rows = ~np.isfinite(res_bar[0]) & (a < b) & np.isfinite(a) & np.isfinite(res_bar[1])
@@ -71,9 +70,9 @@ def test_new_opcode_is_bit_equal_to_the_fp32_model(hiplib, name):
 def test_point_counts_and_sliced_jets(hiplib, P, pad):
     """pad = 0: dense jets, bit-equal to the float32 model (the program holds exact opcodes only).  pad = 3: jets = buf[:, :, :P]
     of a leaf buf whose padding holds NaN -- values and gradient bit-equal again, the padding's gradient exactly +0."""
-    c = C.mixed_case()
+    c = M.mixed_case()
     prog, jets, x, cot = c["prog"], np.ascontiguousarray(c["jets"][:, :, :P]), c["x"][:P], np.ascontiguousarray(c["cot"][:, :P])
-    want_res, want_bar = np.stack(C.run(prog, jets, x, F)), C.adjoint(prog, jets, x, cot, F)
+    want_res, want_bar = np.stack(M.run(prog, jets, x, F)), M.adjoint(prog, jets, x, cot, F)
     if pad == 0:
         res, bar = _device(prog, jets, cot, x)
         _assert_bits(res, want_res, "values")
@@ -193,7 +192,7 @@ def test_switched_system_matches_the_fp64_cpu_evaluation(hiplib, prec, monkeypat
     assert tr.has("k_residual_fwd") and tr.has("k_residual_bwd"), "\n".join(tr.kernels)
     prog_t, nins, _ = next(iter(layer._res_progs.values()))
     ops = set(np.frombuffer(prog_t.cpu().numpy().tobytes(), dtype=M.DT)["op"].tolist())
-    assert {C.OPS["LT"], C.OPS["AND"], C.OPS["SEL"]} <= ops
+    assert {M.OPS["LT"], M.OPS["AND"], M.OPS["SEL"]} <= ops
     for k in SWITCHED:
         want = c["r64"][k]
         err = (res[k].detach().cpu().double() - want).abs().max().item()
@@ -285,7 +284,7 @@ def test_one_sided_advection_trains_on_a_2d_grid(train):
     assert tr.has("k_reduce_nd_jet_bwd<", "D = 2") and tr.has("k_residual_fwd") and tr.has("k_residual_bwd"), tr.kernels
     prog_t, nins, _ = next(iter(layer._res_progs.values()))
     ops = set(np.frombuffer(prog_t.cpu().numpy().tobytes(), dtype=M.DT)["op"].tolist())
-    assert {C.OPS["LT"], C.OPS["SEL"]} <= ops
+    assert {M.OPS["LT"], M.OPS["SEL"]} <= ops
     grads = [t.grad for k in range(6) for t in (net.fc[k].weight, net.fc[k].bias)]
     err = {"loss": abs(loss.item() - c["loss"]) / abs(c["loss"]), "residual": _relerr(res["one_sided"].reshape(-1), c["res"]),
            "dlatent": _relerr(latd.grad, c["dlat"]), "dW": max(_relerr(g, r) for g, r in zip(grads, c["grads"]))}

@@ -1,5 +1,5 @@
 """The opcodes appended to the residual evaluator (TAN SINH COSH ASIN ACOS ATAN ATAN2 POWC POW MIN MAX SIGN STEP) on the device,
-against tests/residual_ext_model.py (whose adjoint rules tests/test_residual_ext_host.py checks against torch's autograd), the way
+against tests/residual_model.py (whose adjoint rules tests/test_residual_ext_host.py checks against torch's autograd), the way
 tests/test_gpu_residual_ops.py holds the first 17: hand-assembled programs through pde._ResidualHip.apply.
 
 * MIN MAX SIGN STEP (comparisons and selects) and POWC with c = 1: values and adjoints BIT-EQUAL to the float32 model on 4096
@@ -25,7 +25,6 @@ import numpy as np
 import pytest
 import torch
 
-from tests import residual_ext_model as X
 from tests import residual_model as M
 
 pytestmark = pytest.mark.gpu
@@ -43,7 +42,7 @@ def _record(key, value):
 
 
 def _n_eq(prog):
-    return int((prog["op"] == X.OPS["OUT"]).sum())
+    return int((prog["op"] == M.OPS["OUT"]).sum())
 
 
 def _apply(prog, jets_t, x=None):
@@ -67,26 +66,26 @@ def _assert_bits(got, want, what):
 
 
 # ---- exact opcodes --------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", X.EXACT_CASES)
+@pytest.mark.parametrize("name", M.EXACT_CASES_EXT)
 def test_exact_opcode_is_bit_equal_to_the_fp32_model(hiplib, name):
-    prog, jets, res_bar = X.exact_case(name)
+    prog, jets, _, res_bar = M.exact_case(name)
     res, bar = _device(prog, jets, res_bar)
-    _assert_bits(res, np.stack(X.run(prog, jets, None, F)), name + " values")
-    _assert_bits(bar, X.adjoint(prog, jets, None, res_bar, F), name + " adjoint")
+    _assert_bits(res, np.stack(M.run(prog, jets, None, F)), name + " values")
+    _assert_bits(bar, M.adjoint(prog, jets, None, res_bar, F), name + " adjoint")
     if name == "POWC_1":            # x^1 = x and d/dx = 1 x^0 = 1, at 0, -0, the infinities and NaN too
         _assert_bits(res[0], jets[0, 0], "x^1")
         _assert_bits(bar[0, 0], res_bar[0], "d x^1")
 
 
 # ---- opcodes of the math library ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", X.TRANS_CASES)
+@pytest.mark.parametrize("name", M.TRANS_CASES_EXT)
 def test_math_library_opcode_within_four_times_torchs_own_error(hiplib, name):
-    prog, jets, cot, _, _, _ = X.trans_reference(name)
+    prog, jets, cot, _, _, _ = M.trans_reference(name)
     res, bar = _device(prog, jets, cot)
-    e_val, e_adj = X.trans_errors(name, res[0], bar[0])
-    y_val, y_adj = X.trans_yardstick(name)
+    e_val, e_adj = M.trans_errors(name, res[0], bar[0])
+    y_val, y_adj = M.trans_yardstick(name)
     b_val, b_adj = M.trans_bound(y_val), M.trans_bound(y_adj)
-    label = name if not name.startswith("POWC_") else "POWC_%.6g" % X.POWC_EXPONENTS[int(name[5:])]
+    label = name if not name.startswith("POWC_") else "POWC_%.6g" % M.POWC_EXPONENTS[int(name[5:])]
     print("%s: value %.3f ulp (yardstick %.3f, bound %.3f); adjoint %.3f units (yardstick %.3f, bound %.3f)"
           % (label, e_val, y_val, b_val, e_adj, y_adj, b_adj))
     _record(label, {"value": {"device_max_ulp": e_val, "cpu_yardstick_ulp": y_val, "bound": b_val},
@@ -123,8 +122,8 @@ def _mixed_case():
         jets[0, 0, :3] = 0.0                           # exact zeros: sign 0, H 1/2, and ties of MIN / MAX with x below
         x = rng.uniform(-1, 1, (1000, 3)).astype(F)
         x[:3, 1] = 0.0
-        _mixed.update(prog=X.program(*ins), jets=jets, x=x, cot=rng.standard_normal((2, 1000)).astype(F))
-        assert set(_mixed["prog"]["op"].tolist()) >= set(X.OPS_EXT.values())
+        _mixed.update(prog=M.program(*ins), jets=jets, x=x, cot=rng.standard_normal((2, 1000)).astype(F))
+        assert set(_mixed["prog"]["op"].tolist()) >= set(M.OPS_EXT.values())
         for v in _mixed.values():
             v.setflags(write=False)
     return _mixed
@@ -140,8 +139,8 @@ def test_point_counts_and_sliced_jets(hiplib, P, pad):
     res, bar = _device(prog, jets, cot, x)
     assert res.shape == (2, P) and bar.shape == jets.shape
     if pad == 0:
-        np.testing.assert_allclose(res, np.stack(X.run(prog, jets, x, np.float64)), rtol=2e-5, atol=2e-5)
-        np.testing.assert_allclose(bar, X.adjoint(prog, jets, x, cot, np.float64), rtol=2e-5, atol=2e-5)
+        np.testing.assert_allclose(res, np.stack(M.run(prog, jets, x, np.float64)), rtol=2e-5, atol=2e-5)
+        np.testing.assert_allclose(bar, M.adjoint(prog, jets, x, cot, np.float64), rtol=2e-5, atol=2e-5)
         return
     buf = torch.full((1, 2, P + pad), float("nan"))
     buf[:, :, :P] = torch.from_numpy(np.array(jets))
@@ -205,7 +204,7 @@ def test_upwinded_power_law_system_matches_the_fp64_cpu_evaluation(hiplib, prec,
     assert tr.has("k_residual_fwd") and tr.has("k_residual_bwd"), "\n".join(tr.kernels)
     prog_t, nins, _ = next(iter(layer._res_progs.values()))
     ops = set(np.frombuffer(prog_t.cpu().numpy().tobytes(), dtype=M.DT)["op"].tolist())
-    assert {X.OPS["MAX"], X.OPS["MIN"], X.OPS["POWC"]} <= ops
+    assert {M.OPS["MAX"], M.OPS["MIN"], M.OPS["POWC"]} <= ops
     # fp64 on the CPU: the reverse-sweep strategy of the same layer class over the oracle's query
     p64 = [(net.fc[k].weight.detach().cpu().double().requires_grad_(True),
             net.fc[k].bias.detach().cpu().double().requires_grad_(True)) for k in range(6)]

@@ -1,12 +1,11 @@
 """Piecewise with relational conditions, And / Or / Not, pi and the other number symbols, Heaviside(a, h0) in PDELayer equations,
-everything that needs no GPU: the model of the opcodes appended after STEP (tests/residual_cond_model.py) against torch's fp64
+everything that needs no GPU: the model of the opcodes appended after STEP (tests/residual_model.py) against torch's fp64
 autograd at the ties, zeros, infinities, NaN and with NaN cotangents; the equation strings on both torch strategies against
 hand-written torch.where formulas; their device programs (``_compile_residual_program(..., extended=True, conditional=True)``)
 through the model against the lambdified functions; and that nothing that compiled before compiles differently."""
 import base64
 import json
 import os
-import re
 import types
 
 import numpy as np
@@ -16,7 +15,6 @@ import torch
 
 from space_time_pde_amd import local_implicit_grid as lig
 from space_time_pde_amd import pde, physics
-from tests import residual_cond_model as C
 from tests import residual_model as M
 from tests import test_residual_ext_host as E
 
@@ -24,36 +22,22 @@ ROOT = E.ROOT
 NAN, INF = float("nan"), float("inf")
 
 
-# ---- tables ---------------------------------------------------------------------------------------------------------------------
-def test_new_opcodes_follow_step_and_renumber_nothing():
-    assert pde._RES_OPS_COND == C.OPS_COND
-    names = ["LT", "LE", "EQ", "NE", "AND", "OR", "NOT", "SEL", "STEPC"]
-    assert [pde._RES_OPS_COND[n] for n in names] == list(range(30, 39))
-    assert max(pde._RES_OPS_EXT.values()) == 29 and pde._RES_MAX_INS == C.MAX_INS == 192
-    with open(os.path.join(ROOT, "include", "stpde_hip.h")) as f:
-        text = f.read()
-    enum = re.search(r"enum \{[^{}]*?(STPDE_RES_LT = STPDE_RES_STEP \+ 1.*?)\};", text, re.S).group(1)
-    assert [t.strip().split("=")[0].strip()[len("STPDE_RES_"):] for t in enum.split(",") if t.strip()] == names
-    assert "#define STPDE_RES_MAX_INS 192" in text
-    assert C.sel_operands(C.sel(191, 190)) == (191, 190)
-
-
 # ---- the model against torch's fp64 autograd ----------------------------------------------------------------------------------------
 def _against_autograd(prog, jets, cot, what):
     jets = np.asarray(jets, dtype=np.float64)
     cot = np.asarray(cot, dtype=np.float64)
     jt = torch.from_numpy(jets.copy()).requires_grad_(True)
-    outs = C.torch_program(prog, jt, None)
+    outs = M.torch_program(prog, jt, None)
     sum((o * torch.from_numpy(cot[k])).sum() for k, o in enumerate(outs)).backward()
-    vals = C.run(prog, jets, None, np.float64)
+    vals = M.run(prog, jets, None, np.float64)
     for k, o in enumerate(outs):
         E._same(vals[k], o.detach().numpy(), "%s value %d" % (what, k))
-    E._same(C.adjoint(prog, jets, None, cot, np.float64), jt.grad.numpy(), what + " adjoint")
+    E._same(M.adjoint(prog, jets, None, cot, np.float64), jt.grad.numpy(), what + " adjoint")
 
 
-@pytest.mark.parametrize("name", C.EXACT_CASES)
+@pytest.mark.parametrize("name", M.EXACT_CASES_COND)
 def test_model_matches_torch_autograd_on_the_exact_cases(name):
-    prog, jets, cot = C.exact_case(name)
+    prog, jets, _, cot = M.exact_case(name)
     _against_autograd(prog, jets, cot, name)
 
 
@@ -61,21 +45,21 @@ def test_the_models_conventions_literally():
     e = M.edge_index
     # comparisons: IEEE, a mask is never NaN, nothing reaches the operands except through the MUL
     for name, fn in (("LT", np.less), ("LE", np.less_equal), ("EQ", np.equal), ("NE", np.not_equal)):
-        prog, jets, cot = C.exact_case(name)
-        val = C.run(prog, jets, None, np.float32)
+        prog, jets, _, cot = M.exact_case(name)
+        val = M.run(prog, jets, None, np.float32)
         assert all(set(np.unique(v)) <= {0.0, 1.0} for v in val[:3])
         assert np.array_equal(val[0], fn(jets[0, 0], jets[0, 1]).astype(np.float32))
         for a, b in ((NAN, 1.0), (1.0, NAN), (NAN, NAN)):
             assert val[0][e(a, b)] == (1.0 if name == "NE" else 0.0)
         assert val[0][e(0.0, -0.0)] == (1.0 if name in ("LE", "EQ") else 0.0)
         assert val[0][:64].tolist() == [1.0 if name in ("LE", "EQ") else 0.0] * 64            # the tied rows
-        bar = C.adjoint(prog, jets, None, cot, np.float32)
+        bar = M.adjoint(prog, jets, None, cot, np.float32)
         assert not bar[0, 1].view(np.int32).any()                                            # b: only ever compared
         with np.errstate(all="ignore"):
             assert M.same_bits(bar[0, 0], np.float32(0) + cot[3] * val[0]).all()                  # (an accumulator from +0)
     # SEL: the operand not taken receives exactly +0, also under a NaN or infinite cotangent
-    prog, jets, cot = C.exact_case("SEL")
-    bar = C.adjoint(prog, jets, None, cot, np.float32)
+    prog, jets, _, cot = M.exact_case("SEL")
+    bar = M.adjoint(prog, jets, None, cot, np.float32)
     a, b = jets[0, 0], jets[0, 1]
     bad = ~np.isfinite(cot[0])
     assert bad.sum() > 500 and (bad & (a < b)).sum() > 100 and (bad & ~(a < b)).sum() > 100
@@ -86,20 +70,20 @@ def test_the_models_conventions_literally():
     rows = bad & (a < b) & np.isfinite(a)
     assert rows.any() and np.isfinite(bar[0, 1][rows]).all() and np.isnan(bar[0, 0][rows & np.isnan(cot[0])]).all()
     # a dead sqrt(0): the zero cotangent of the branch not taken becomes 0 * 0.5 / 0 = NaN in sqrt's own rule, as in torch
-    prog, jets, cot = C.exact_case("SEL_DEAD_SQRT")
-    val, = C.run(prog, jets, None, np.float32)
-    bar = C.adjoint(prog, jets, None, cot, np.float32)[0, 0]
+    prog, jets, _, cot = M.exact_case("SEL_DEAD_SQRT")
+    val, = M.run(prog, jets, None, np.float32)
+    bar = M.adjoint(prog, jets, None, cot, np.float32)[0, 0]
     for z in (0.0, -0.0):
         assert val[e(z)] == 0.0 and np.isnan(bar[e(z)])
     assert val[e(1.0)] == 1.0 and bar[e(1.0)] == 0.5 and np.isnan(bar[e(-1.0)]) and val[e(-1.0)] == 0.0
     # no default: NaN where no condition holds
-    prog, jets, cot = C.exact_case("SEL_NAN_DEFAULT")
-    val, = C.run(prog, jets, None, np.float32)
+    prog, jets, _, cot = M.exact_case("SEL_NAN_DEFAULT")
+    val, = M.run(prog, jets, None, np.float32)
     assert np.isnan(val[e(1.0, -1.0)]) and val[e(-1.0, 1.0)] == -1.0 and val[e(1.0, 1.0)] == 1.0
     # STEPC
-    for k, c in enumerate(C.STEPC_VALUES):
-        prog, jets, cot = C.exact_case("STEPC_%d" % k)
-        val = C.run(prog, jets, None, np.float32)
+    for k, c in enumerate(M.STEPC_VALUES):
+        prog, jets, _, cot = M.exact_case("STEPC_%d" % k)
+        val = M.run(prog, jets, None, np.float32)
         for x, w in ((0.0, c), (-0.0, c), (1.0, 1.0), (-1.0, 0.0), (INF, 1.0), (-INF, 0.0)):
             assert val[0][e(x)] == w, (c, x)
         assert np.isnan(val[0][e(NAN)])
@@ -107,9 +91,9 @@ def test_the_models_conventions_literally():
 
 def test_hand_written_programs_are_checked_before_they_reach_a_kernel():
     with pytest.raises(AssertionError):
-        C.program(("JET", 0, 0), ("LT", 0, 1))                                   # operand 1 is not an earlier instruction
+        M.program(("JET", 0, 0), ("LT", 0, 1))                                   # operand 1 is not an earlier instruction
     with pytest.raises(AssertionError):
-        C.program(("JET", 0, 0), ("LT", 0, 0), ("SEL", 1, C.sel(0, 2)))
+        M.program(("JET", 0, 0), ("LT", 0, 0), ("SEL", 1, M.sel(0, 2)))
 
 
 # ---- the equation strings on both torch strategies -------------------------------------------------------------------------------------
@@ -279,7 +263,7 @@ def _layer_program(layer, combo, extended):
 
 
 def _ops(prog):
-    return {C.NAMES[o] for o in prog["op"].tolist()}
+    return {M.NAMES[o] for o in prog["op"].tolist()}
 
 
 @pytest.mark.parametrize("k", range(len(STRINGS)), ids=_IDS)
@@ -292,15 +276,15 @@ def test_string_compiles_only_when_extended_and_the_program_equals_the_lambdifie
     comp = _compile(layer)
     assert comp is not None
     prog, uses_x = comp
-    assert EMITS[k] <= _ops(prog) and (EMITS[k] or not (_ops(prog) & set(C.OPS_COND))), _ops(prog)
+    assert EMITS[k] <= _ops(prog) and (EMITS[k] or not (_ops(prog) & set(M.OPS_COND))), _ops(prog)
     for i, (op, a, b, c) in enumerate(prog.tolist()):                                  # SSA: the kernels do not check
-        assert all(0 <= o < i for o in C.operands(C.NAMES[op], a, b)), (i, C.NAMES[op], a, b)
+        assert all(0 <= o < i for o in M.operands(M.NAMES[op], a, b)), (i, M.NAMES[op], a, b)
     stream_of, pairs = E._streams(p)
     x = torch.rand(1, 65, 3, generator=torch.Generator().manual_seed(4), dtype=torch.float64)
     jets = _Field(*field).jets(x, pairs)
     cols = [x[..., i:i + 1] for i in range(3)]
     want = p.fn(*(cols + [jets[stream_of[a[1]], a[0]].reshape(1, 65, 1) for a in p.atoms])).reshape(-1).numpy()
-    got, = C.run(prog, jets.numpy(), x.reshape(-1, 3).numpy(), np.float64)
+    got, = M.run(prog, jets.numpy(), x.reshape(-1, 3).numpy(), np.float64)
     np.testing.assert_allclose(got, want, rtol=2e-6, atol=2e-6, equal_nan=True)
 
 
@@ -311,14 +295,14 @@ def test_the_encodings_the_compiler_emits():
     def comp(e):
         r = pde._compile_residual_program([e], [x], slots, extended=True, conditional=True)
         assert r is not None, e
-        return [(C.NAMES[o], a, b, c) for o, a, b, c in r[0].tolist()]
+        return [(M.NAMES[o], a, b, c) for o, a, b, c in r[0].tolist()]
 
     # > and >= are LT and LE with the operands swapped; the chain is built from the last branch backwards
     got = comp(sympy.Piecewise((j, j > k), (k, j >= 0), (x, True)))
     assert got == [("X", 0, 0, 0.0), ("JET", 0, 0, 0.0), ("CONST", 0, 0, 0.0), ("LE", 2, 1, 0.0), ("JET", 0, 1, 0.0),
-                   ("SEL", 3, C.sel(4, 0), 0.0), ("LT", 4, 1, 0.0), ("SEL", 6, C.sel(1, 5), 0.0), ("OUT", 7, 0, 0.0)]
+                   ("SEL", 3, M.sel(4, 0), 0.0), ("LT", 4, 1, 0.0), ("SEL", 6, M.sel(1, 5), 0.0), ("OUT", 7, 0, 0.0)]
     got = comp(sympy.Piecewise((j, j < k)))                                            # no default: CONST NaN
-    assert got[0][0] == "CONST" and np.isnan(got[0][3]) and got[-2] == ("SEL", 3, C.sel(1, 0), 0.0)
+    assert got[0][0] == "CONST" and np.isnan(got[0][3]) and got[-2] == ("SEL", 3, M.sel(1, 0), 0.0)
     # number symbols: the nearest float32, as an operand and as a POWC exponent; only the atoms are folded
     f32 = lambda v: float(np.float32(v))                                               # noqa: E731
     assert comp(sympy.pi * j)[:2] in ([("CONST", 0, 0, f32(np.pi)), ("JET", 0, 0, 0.0)], [("JET", 0, 0, 0.0), ("CONST", 0, 0, f32(np.pi))])
@@ -403,4 +387,4 @@ def test_extended_programs_of_the_parent_are_byte_identical():
         assert prog.tobytes() == E._layer_program(layer, w["combo"], True)[0].tobytes()       # and without the new switch
         assert prog.tobytes() == base64.b64decode(w["program"]), key
         assert len(prog) == w["nins"] and bool(uses_x) == w["uses_x"]
-        assert not (_ops(prog) & set(C.OPS_COND)) and _ops(prog) & {"MAX", "MIN", "POWC"}
+        assert not (_ops(prog) & set(M.OPS_COND)) and _ops(prog) & {"MAX", "MIN", "POWC"}

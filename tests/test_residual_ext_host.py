@@ -1,12 +1,11 @@
 """Max / Min / sign / Heaviside, real and expression powers, tan sinh cosh asin acos atan atan2 in PDELayer equations, everything
-that needs no GPU: the model of the appended opcodes (tests/residual_ext_model.py) against torch's fp64 autograd at the ties, zeros,
+that needs no GPU: the model of the appended opcodes (tests/residual_model.py) against torch's fp64 autograd at the ties, zeros,
 infinities, NaN, base 0 and negative bases; the equation strings that could not run on both torch strategies against hand-written
 formulas; their device programs (``_compile_residual_program(..., extended=True)``) through the model against the lambdified
 functions; and that nothing that compiled before compiles differently."""
 import base64
 import json
 import os
-import re
 import types
 
 import numpy as np
@@ -15,24 +14,10 @@ import sympy
 import torch
 
 from space_time_pde_amd import pde, physics
-from tests import residual_ext_model as X
 from tests import residual_model as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN, INF = float("nan"), float("inf")
-
-
-# ---- tables ---------------------------------------------------------------------------------------------------------------------
-def test_appended_opcodes_follow_out_and_renumber_nothing():
-    assert pde._RES_OPS == M.OPS and len(pde._RES_OPS) == 17
-    assert pde._RES_OPS_EXT == X.OPS_EXT
-    names = ["TAN", "SINH", "COSH", "ASIN", "ACOS", "ATAN", "ATAN2", "POWC", "POW", "MIN", "MAX", "SIGN", "STEP"]
-    assert [pde._RES_OPS_EXT[n] for n in names] == list(range(17, 30))
-    with open(os.path.join(ROOT, "include", "stpde_hip.h")) as f:
-        enum = re.search(r"enum \{\s*(STPDE_RES_JET.*?)\};", f.read(), re.S).group(1)
-    header = [t.strip().split("=")[0].strip()[len("STPDE_RES_"):] for t in enum.split(",") if t.strip()]
-    both = dict(pde._RES_OPS, **pde._RES_OPS_EXT)
-    assert header == sorted(both, key=both.get)
 
 
 # ---- the model's adjoints against torch's fp64 autograd ---------------------------------------------------------------------------
@@ -51,21 +36,21 @@ def _against_autograd(prog, jets, cot, what):
     jets = np.asarray(jets, dtype=np.float64)
     cot = np.asarray(cot, dtype=np.float64)
     jt = torch.from_numpy(jets.copy()).requires_grad_(True)
-    outs = X.torch_program(prog, jt, None)
+    outs = M.torch_program(prog, jt, None)
     sum((o * torch.from_numpy(cot[k])).sum() for k, o in enumerate(outs)).backward()
-    vals = X.run(prog, jets, None, np.float64)
+    vals = M.run(prog, jets, None, np.float64)
     for k, o in enumerate(outs):
         _same(vals[k], o.detach().numpy(), "%s value %d" % (what, k))
-    _same(X.adjoint(prog, jets, None, cot, np.float64), jt.grad.numpy(), what + " adjoint")
+    _same(M.adjoint(prog, jets, None, cot, np.float64), jt.grad.numpy(), what + " adjoint")
 
 
 @pytest.mark.parametrize("name", ["MIN", "MAX", "SIGN", "STEP"])
 def test_min_max_sign_step_at_ties_zeros_infinities_and_nan(name):
-    prog, jets, cot = X.exact_case(name)
+    prog, jets, _, cot = M.exact_case(name)
     _against_autograd(prog, jets, cot, name)
     # the conventions, literally (cotangent 1 on the edge rows)
-    bar = X.adjoint(prog, jets, None, cot, np.float32)
-    val = X.run(prog, jets, None, np.float32)
+    bar = M.adjoint(prog, jets, None, cot, np.float32)
+    val = M.run(prog, jets, None, np.float32)
     if name in ("MIN", "MAX"):
         for a, b in ((0.0, 0.0), (0.0, -0.0), (-0.0, 0.0), (1.0, 1.0), (INF, INF), (-INF, -INF)):
             i = M.edge_index(a, b)
@@ -99,10 +84,10 @@ def test_powc_at_base_zero_and_negative_bases(c):
     x = _pow_inputs()
     if c == -0.5:       # torch evaluates x ** -0.5 as rsqrt, -inf at -0; the evaluator's is the IEEE pow, +inf at both zeros
         x = np.delete(x, 1)
-    prog = X.program(("JET", 0, 0), ("POWC", 0, 0, c), ("OUT", 1, 0))
+    prog = M.program(("JET", 0, 0), ("POWC", 0, 0, c), ("OUT", 1, 0))
     cot = np.random.default_rng(6).standard_normal((1, len(x)))
     _against_autograd(prog, x[None, None], cot, "POWC %r" % c)
-    bar = X.adjoint(prog, x[None, None], None, np.ones((1, len(x))), np.float64)[0, 0]
+    bar = M.adjoint(prog, x[None, None], None, np.ones((1, len(x))), np.float64)[0, 0]
     neg = x < 0
     if c >= 1:          # a regular point: c 0^(c-1), no division by the base
         assert bar[0] == (1.0 if c == 1 else 0.0)
@@ -116,7 +101,7 @@ def test_pow_at_base_zero_negative_bases_and_exponent_zero():
     x = _pow_inputs()
     e = np.array([-2.0, -0.5, 0.0, -0.0, 0.5, 1.0, 1.5, 2.0, 3.0])
     a, b = np.repeat(x, len(e)), np.tile(e, len(x))
-    prog = X.program(("JET", 0, 0), ("JET", 0, 1), ("POW", 0, 1), ("OUT", 2, 0), ("CONST", 0, 0, 2.0), ("POW", 4, 1), ("OUT", 5, 1))
+    prog = M.program(("JET", 0, 0), ("JET", 0, 1), ("POW", 0, 1), ("OUT", 2, 0), ("CONST", 0, 0, 2.0), ("POW", 4, 1), ("OUT", 5, 1))
     cot = np.random.default_rng(7).standard_normal((2, len(a)))
     _against_autograd(prog, np.stack([a, b])[None], cot, "POW")
 
@@ -130,13 +115,13 @@ def test_math_library_opcodes_against_autograd(name):
         x = np.concatenate([[0.0, -0.0, 1.0, -1.0], rng.uniform(-3, 3, 60)])
     if name == "ATAN2":
         jets = np.stack([x, np.concatenate([[0.0, 1.0, -0.0, 0.0], rng.uniform(-3, 3, 60)])])[None]
-        prog = X.program(("JET", 0, 0), ("JET", 0, 1), (name, 0, 1), ("OUT", 2, 0))
+        prog = M.program(("JET", 0, 0), ("JET", 0, 1), (name, 0, 1), ("OUT", 2, 0))
     else:
         jets = x[None, None]
-        prog = X.program(("JET", 0, 0), (name, 0), ("OUT", 1, 0))
+        prog = M.program(("JET", 0, 0), (name, 0), ("OUT", 1, 0))
     _against_autograd(prog, jets, rng.standard_normal((1, len(x))), name)
     if name in ("ASIN", "ACOS"):
-        bar = X.adjoint(prog, jets, None, np.ones((1, len(x))), np.float64)[0, 0]
+        bar = M.adjoint(prog, jets, None, np.ones((1, len(x))), np.float64)[0, 0]
         assert bar[0] == bar[1] == (INF if name == "ASIN" else -INF)
 
 
@@ -247,14 +232,14 @@ def test_string_compiles_only_when_extended_and_the_program_equals_the_lambdifie
     if eq.endswith("**2.0"):                     # an integral Float exponent: the exact POWI
         assert prog["op"].tolist() == [M.OPS["JET"], M.OPS["POWI"], M.OPS["OUT"]] and prog["b"][1] == 2
     else:
-        assert set(prog["op"].tolist()) & set(X.OPS_EXT.values())
+        assert set(prog["op"].tolist()) & set(M.OPS_EXT.values())
     stream_of, pairs = _streams(p)
     g = torch.Generator().manual_seed(4)
     x = torch.rand(1, 65, 3, generator=g, dtype=torch.float64)
     jets = _Field(*field).jets(x, pairs)
     cols = [x[..., i:i + 1] for i in range(3)]
     want = p.fn(*(cols + [jets[stream_of[a[1]], a[0]].reshape(1, 65, 1) for a in p.atoms])).reshape(-1).numpy()
-    got, = X.run(prog, jets.numpy(), x.reshape(-1, 3).numpy(), np.float64)
+    got, = M.run(prog, jets.numpy(), x.reshape(-1, 3).numpy(), np.float64)
     np.testing.assert_allclose(got, want, rtol=2e-6, atol=2e-6)
 
 

@@ -4,6 +4,11 @@ The fp64 adjoint model (the rules of k_residual_bwd) must agree with torch's fp6
 own operators, for every opcode: then the device tests, which hold the kernel to the model, cannot share a wrong rule with it.
 The float32 model is pinned to torch's conventions at the singular points, and an equation set whose compiled program contains
 all 17 opcodes is checked against the lambdified equations in fp64."""
+import hashlib
+import json
+import os
+import re
+
 import numpy as np
 import pytest
 import sympy
@@ -13,9 +18,68 @@ from space_time_pde_amd import pde as P
 from tests import residual_model as M
 
 
-def test_model_tables_are_the_packages():
-    assert M.OPS == P._RES_OPS and M.DT == P._RES_DT
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OPCODES = ["JET", "X", "CONST", "ADD", "SUB", "MUL", "DIV", "NEG", "POWI", "SIN", "COS", "EXP", "LOG", "SQRT", "TANH", "ABS", "OUT",
+           "TAN", "SINH", "COSH", "ASIN", "ACOS", "ATAN", "ATAN2", "POWC", "POW", "MIN", "MAX", "SIGN", "STEP",
+           "LT", "LE", "EQ", "NE", "AND", "OR", "NOT", "SEL", "STEPC"]
+
+
+def test_header_package_and_model_share_one_opcode_table():
+    """One numbering in three places: the header's enum, pde._RES_OPS and the model's OPS."""
+    with open(os.path.join(ROOT, "include", "stpde_hip.h")) as f:
+        text = f.read()
+    enums = re.findall(r"enum \{([^{}]*STPDE_RES_[^{}]*)\};", text)
+    assert len(enums) == 1
+    header = [t.strip() for t in enums[0].split(",") if t.strip()]
+    assert header[0] == "STPDE_RES_JET = 0" and not any("=" in t for t in header[1:])        # numbered 0, 1, 2, ... in order
+    header[0] = "STPDE_RES_JET"
+    assert header == ["STPDE_RES_" + n for n in OPCODES] and len(OPCODES) == 39
+    want = {n: k for k, n in enumerate(OPCODES)}
+    assert P._RES_OPS == want and M.OPS == want
+    assert [M.OPS[n] for n in M.OPS_EXT] == list(range(17, 30)) and [M.OPS[n] for n in M.OPS_COND] == list(range(30, 39))
+    assert "#define STPDE_RES_MAX_INS 192" in text and P._RES_MAX_INS == M.MAX_INS == 192
+    assert P._RES_DT == M.DT
+    assert M.sel_operands(M.sel(191, 190)) == (191, 190)
     assert len(M.chain_program()[0]) == P._RES_MAX_INS
+
+
+def _canonical_digest(arrays, dtype):
+    """SHA-256 of the arrays as little-endian ``dtype``, every NaN replaced by the one canonical NaN (the models compare the
+    position of a NaN, not its payload)."""
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.array(a, dtype=np.dtype(dtype).newbyteorder("<"))
+        a[np.isnan(a)] = np.nan
+        h.update(repr(a.shape).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def _parent_cases():
+    """(key, prog, jets, x, cot): every exact case, the mixed case and the 192-instruction chain on the inputs of its device test."""
+    for name in M.EXACT_CASES:
+        yield (name,) + M.exact_case(name)
+    c = M.mixed_case()
+    yield "mixed", c["prog"], c["jets"], c["x"], c["cot"]
+    prog, n_eq = M.chain_program()
+    rng = np.random.default_rng(5)
+    yield "chain", prog, rng.uniform(0.5, 2.0, (2, 1, 300)).astype(np.float32), None, rng.standard_normal((n_eq, 300)).astype(np.float32)
+
+
+def test_folded_model_reproduces_the_parents_exact_results():
+    """tests/golden/residual_model_parent.json: digests of ``run`` and ``adjoint``, float32 and float64, recorded with the three
+    layered models this one replaced (residual_model, residual_ext_model for MIN .. POWC_1, residual_cond_model for LT .. STEPC_2
+    and the mixed case).  These cases hold only IEEE add, subtract, multiply, divide, sqrt, comparisons and selects, so the bits
+    do not depend on the numpy build."""
+    with open(os.path.join(ROOT, "tests", "golden", "residual_model_parent.json")) as f:
+        want = json.load(f)
+    cases = list(_parent_cases())
+    assert [c[0] for c in cases] == list(want) and len(want) == len(M.EXACT_CASES) + 2 == 39
+    for key, prog, jets, x, cot in cases:
+        for dt in ("float32", "float64"):
+            got = {"run": _canonical_digest(M.run(prog, jets, x, np.dtype(dt).type), dt),
+                   "adjoint": _canonical_digest([M.adjoint(prog, jets, x, cot, np.dtype(dt).type)], dt)}
+            assert got == want[key][dt], (key, dt)
 
 
 def _autograd64(prog, jets, x, res_bar):
@@ -35,11 +99,11 @@ def _same_class(a, b):
 
 
 def _cases():
-    for name in M.EXACT_CASES:
+    for name in M.EXACT_CASES_BASE:
         yield (name,) + M.exact_case(name)
-    for name in M.TRANS:
-        x, g = M.sweep(name), M.cotangent(M.SWEEP_N, M.OPS[name])
-        yield name, M.program(("JET", 0, 0), (name, 0), ("OUT", 1, 0)), x[None, None], None, g[None]
+    for name in M.TRANS_CASES_BASE:
+        prog, jets, cot = M.trans_case(name)
+        yield name, prog, jets, None, cot
         e = np.array(M.EDGES, dtype=np.float32)
         yield name + "_edges", M.program(("JET", 0, 0), (name, 0), ("OUT", 1, 0)), e[None, None], None, np.ones((1, len(e)))
     prog, n_eq = M.chain_program()
@@ -88,7 +152,7 @@ def test_fp32_model_has_torchs_conventions_at_the_singular_points():
         model = M.adjoint(prog, jets, x, res_bar, np.float32)[0, ch, i]
         jt = torch.from_numpy(np.array(jets)).requires_grad_(True)
         res = M.torch_program(prog, jt, None)
-        (res[0] * torch.from_numpy(res_bar[0])).sum().backward()
+        (res[0] * torch.from_numpy(np.array(res_bar[0]))).sum().backward()
         for got in (model, jt.grad[0, ch, i].item()):
             assert (np.isnan(got) and np.isnan(value)) or got == value, (name, at, got, value)
 
@@ -107,14 +171,14 @@ def test_ulp_err_counts_float32_steps():
 def test_transcendental_sweeps_and_yardsticks():
     """The sweeps have the size and the ranges the device tests state, and torch's own float32 evaluation -- the yardstick --
     stays within a few ulp on them (so that 4 x max(1, yardstick) is a bound worth the name)."""
-    for name, t in M.TRANS.items():
-        x = M.sweep(name)
+    for name, (lo, hi) in M.SWEEP_RANGE.items():
+        x = M.trans_case(name)[1][0, 0]
         assert x.shape == (32768,) and x.dtype == np.float32
-        assert x.min() == np.float32(t.lo) and x.max() == np.float32(t.hi)
+        assert x.min() == np.float32(lo) and x.max() == np.float32(hi)
         val, adj = M.trans_yardstick(name)
         print("%s: torch float32 on the CPU reaches %.3f ulp (value), %.3f units (adjoint)" % (name, val, adj))
         assert 0 < val <= 4 and 0 < adj <= 8, (name, val, adj)
-    x = M.sweep("TANH")
+    x = M.trans_case("TANH")[1][0, 0]
     assert np.signbit(x[x == 0]).tolist() == [False, True] and (np.tanh(x.astype(np.float64)).astype(np.float32) == 1).any()
 
 

@@ -669,7 +669,14 @@ int stpde_resample3d(const stpde_resample_desc* d, int mode, const float* in, co
  *   STEPC (a)  Heaviside with H(0) = c, H(NaN) = NaN (STEP's c is 0 and means 1/2)
  *   Masks, comparison operands and STEPC have adjoint 0.
  * res [n_eq][P]; the adjoint adds d loss / d jets into jets_bar (same layout as jets, zero-filled by the caller).
- * The coordinates x are not differentiated here (the jets already are the coordinate derivatives). */
+ * The coordinates x are not differentiated here (the jets already are the coordinate derivatives).
+ * Coefficients in device memory (the _coef entry points only): a late-bound CONST -- op = CONST, b = 1, a = k, c = 0 -- is
+ *   the value of coefficient k of the stpde_res_coefs record: value[k][0] for every point, or value[k][p / n_per_batch] (one per
+ *   batch element) where per_batch[k] != 0.  No opcode is added: every other program holds CONST with a = b = 0, and
+ *   stpde_residual_fwd / _bwd read a CONST's c whatever its b.  The value is loaded when the kernel runs, not when the program
+ *   is compiled: an in-place update is seen by the next launch, and by the next replay of a captured one.  The adjoint adds
+ *   sum over the points of d loss / d coefficient into bar[k][0] (or [p / n_per_batch]): one sum per 256-point block, then
+ *   one atomic per block. */
 #define STPDE_RES_MAX_INS 192
 enum {
   STPDE_RES_JET = 0, STPDE_RES_X, STPDE_RES_CONST, STPDE_RES_ADD, STPDE_RES_SUB, STPDE_RES_MUL, STPDE_RES_DIV,
@@ -691,6 +698,24 @@ int stpde_residual_fwd(const stpde_res_ins* prog_dev, int nins, int n_eq, int n_
 int stpde_residual_bwd(const stpde_res_ins* prog_dev, int nins, int n_eq, int n_out, int P, const float* jets,
                        long ld_stream, long ld_channel, const float* x, const float* res_bar, float* jets_bar,
                        void* stream);
+/* The same for a program with late-bound CONSTs.  The record is caller-owned host memory, read during the call.  The points
+ * are B batch elements of n_per_batch each, batch-major: P = B * n_per_batch (anything else, n outside 1 .. 8 or a null
+ * value[k] is STPDE_E_BADARG). */
+#define STPDE_RES_MAX_COEF 8
+typedef struct {
+  int n;                 /* coefficients read by the program, <= STPDE_RES_MAX_COEF */
+  int n_per_batch;       /* N; P must equal B * N */
+  int det;               /* bwd: bar[k] address long accumulators (as STPDE_LOSS_DET), not floats */
+  int per_batch[STPDE_RES_MAX_COEF];      /* 0: value[k][0] for every point; 1: value[k][b] */
+  const float* value[STPDE_RES_MAX_COEF]; /* device */
+  float* bar[STPDE_RES_MAX_COEF];         /* bwd only; NULL = no gradient wanted; zero-filled by the caller */
+} stpde_res_coefs;
+int stpde_residual_coef_fwd(const stpde_res_ins* prog_dev, int nins, int n_eq, int n_out, int P, const float* jets,
+                            long ld_stream, long ld_channel, const float* x, float* res, const stpde_res_coefs* coefs,
+                            void* stream);
+int stpde_residual_coef_bwd(const stpde_res_ins* prog_dev, int nins, int n_eq, int n_out, int P, const float* jets,
+                            long ld_stream, long ld_channel, const float* x, const float* res_bar, float* jets_bar,
+                            const stpde_res_coefs* coefs, void* stream);
 
 /* ---- a11: loss reductions of the train step (experiments/rb2d/train.py:69-76) -------------------------------
  * out_sum += sum_i f(a[i] - b[i]) with f = |d| (L1), d^2 (L2) or smooth-l1 with beta 1 (b == NULL: against 0);

@@ -92,6 +92,14 @@ class ResampleDesc(C.Structure):
                 ("fz", C.c_int), ("fx", C.c_int)]
 
 
+RES_MAX_COEF = 8   # STPDE_RES_MAX_COEF
+
+
+class ResCoefs(C.Structure):        # stpde_res_coefs
+    _fields_ = [("n", C.c_int), ("n_per_batch", C.c_int), ("det", C.c_int), ("per_batch", C.c_int * RES_MAX_COEF),
+                ("value", C.c_void_p * RES_MAX_COEF), ("bar", C.c_void_p * RES_MAX_COEF)]
+
+
 BN_REP = 16        # STPDE_BN_REP: replicas of the BatchNorm reduction scratch (include/stpde_hip.h)
 DET_K = 6          # STPDE_DET_K: 64-bit windows of a deterministic-mode long accumulator (12 floats of storage per element)
 # Deterministic mode (round 6; STPDE_DETERMINISTIC=1 or ``_lib.deterministic = True``): every sum the step accumulates with
@@ -294,6 +302,10 @@ _SIGNATURES = {
     "stpde_residual_fwd": ([_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, C.c_long, C.c_long, _VP, _VP, _VP], C.c_int),
     "stpde_residual_bwd": ([_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, C.c_long, C.c_long, _VP, _VP, _VP, _VP],
                            C.c_int),
+    "stpde_residual_coef_fwd": ([_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, C.c_long, C.c_long, _VP, _VP,
+                                 C.POINTER(ResCoefs), _VP], C.c_int),
+    "stpde_residual_coef_bwd": ([_VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP, C.c_long, C.c_long, _VP, _VP, _VP,
+                                 C.POINTER(ResCoefs), _VP], C.c_int),
     "stpde_resample3d": ([C.POINTER(ResampleDesc), C.c_int, _VP, _VP, _VP, _VP], C.c_int),
     "stpde_det_finalize": ([_VP, C.c_long, _VP, _VP], C.c_int),
     "stpde_bn_fwd": ([C.POINTER(BnDesc)] + [_VP] * 10, C.c_int),

@@ -74,12 +74,15 @@ __device__ __forceinline__ float res_eval_ext(const stpde_res_ins& in, const flo
   }
 }
 
-__device__ __forceinline__ float res_eval(const stpde_res_ins& in, const float* v, const ResArgs& a, int p) {
+// COEF: a CONST with b != 0 is late-bound -- the value of coefficient a, staged per block in coef (k_residual_coef_*); without
+// the flag every CONST is its c, whatever b holds (the programs of k_residual_fwd / _bwd carry b = 0).
+template <bool COEF>
+__device__ __forceinline__ float res_eval(const stpde_res_ins& in, const float* v, const ResArgs& a, int p, const float* coef) {
   if (in.op > STPDE_RES_OUT) return res_eval_ext(in, v);
   switch (in.op) {
     case STPDE_RES_JET: return a.jets[(size_t)in.a * a.ld_s + (size_t)in.b * a.ld_c + p];
     case STPDE_RES_X: return a.x[(size_t)p * 3 + in.a];
-    case STPDE_RES_CONST: return in.c;
+    case STPDE_RES_CONST: return (COEF && in.b != 0) ? coef[in.a & (STPDE_RES_MAX_COEF - 1)] : in.c;
     case STPDE_RES_ADD: return v[in.a] + v[in.b];
     case STPDE_RES_SUB: return v[in.a] - v[in.b];
     case STPDE_RES_MUL: return v[in.a] * v[in.b];
@@ -106,7 +109,7 @@ __global__ __launch_bounds__(256) void k_residual_fwd(ResArgs a) {
   float v[RES_MAX];
   for (int i = 0; i < a.nins; ++i) {
     const stpde_res_ins in = prog[i];
-    v[i] = res_eval(in, v, a, p);
+    v[i] = res_eval<false>(in, v, a, p, nullptr);
     if (in.op == STPDE_RES_OUT) a.res[(size_t)in.b * a.P + p] = v[i];
   }
 }
@@ -162,6 +165,39 @@ __device__ __forceinline__ void res_bwd_ext(const stpde_res_ins& in, int i, cons
   }
 }
 
+// The reverse rule of instruction i at point p (its adjoint register g[i] is complete: every reader comes later in the program).
+__device__ __forceinline__ void res_bwd_step(const stpde_res_ins& in, int i, const float* v, float* g, const ResArgs& a, int p) {
+  const float gi = g[i];
+  if (in.op > STPDE_RES_OUT) {
+    res_bwd_ext(in, i, v, g, gi);
+    return;
+  }
+  switch (in.op) {
+    case STPDE_RES_OUT: g[in.a] += a.res_bar[(size_t)in.b * a.P + p]; break;
+    case STPDE_RES_JET: {
+      float* dst = a.jets_bar + (size_t)in.a * a.ld_s + (size_t)in.b * a.ld_c + p;   // this thread owns point p
+      *dst += gi;
+      break;
+    }
+    case STPDE_RES_ADD: g[in.a] += gi; g[in.b] += gi; break;
+    case STPDE_RES_SUB: g[in.a] += gi; g[in.b] -= gi; break;
+    case STPDE_RES_MUL: g[in.a] += gi * v[in.b]; g[in.b] += gi * v[in.a]; break;
+    case STPDE_RES_DIV: g[in.a] += gi / v[in.b]; g[in.b] -= gi * v[i] / v[in.b]; break;
+    case STPDE_RES_NEG: g[in.a] -= gi; break;
+    case STPDE_RES_POWI:   // d(x^n)/dx = n x^(n-1), evaluated without dividing by x (x = 0 is a regular point for n >= 1)
+      if (in.b != 0) g[in.a] += gi * (float)in.b * res_ipow(v[in.a], in.b - 1);
+      break;
+    case STPDE_RES_SIN: g[in.a] += gi * cosf(v[in.a]); break;
+    case STPDE_RES_COS: g[in.a] -= gi * sinf(v[in.a]); break;
+    case STPDE_RES_EXP: g[in.a] += gi * v[i]; break;
+    case STPDE_RES_LOG: g[in.a] += gi / v[in.a]; break;
+    case STPDE_RES_SQRT: g[in.a] += gi * 0.5f / v[i]; break;
+    case STPDE_RES_TANH: g[in.a] += gi * (1.f - v[i] * v[i]); break;
+    case STPDE_RES_ABS: g[in.a] += v[in.a] > 0.f ? gi : (v[in.a] < 0.f ? -gi : 0.f); break;   // torch: sign(0) = 0
+    default: break;   // X, CONST: the coordinates are not differentiated on this path
+  }
+}
+
 __global__ __launch_bounds__(256) void k_residual_bwd(ResArgs a) {
   __shared__ stpde_res_ins prog[RES_MAX];
   for (int i = threadIdx.x; i < a.nins; i += 256) prog[i] = a.prog[i];
@@ -170,40 +206,95 @@ __global__ __launch_bounds__(256) void k_residual_bwd(ResArgs a) {
   if (p >= a.P) return;
   float v[RES_MAX], g[RES_MAX];
   for (int i = 0; i < a.nins; ++i) {
-    v[i] = res_eval(prog[i], v, a, p);
+    v[i] = res_eval<false>(prog[i], v, a, p, nullptr);
     g[i] = 0.f;
   }
   for (int i = a.nins - 1; i >= 0; --i) {
     const stpde_res_ins in = prog[i];
-    float gi = g[i];
-    if (in.op > STPDE_RES_OUT) {
-      res_bwd_ext(in, i, v, g, gi);
+    res_bwd_step(in, i, v, g, a, p);
+  }
+}
+
+// ---- the same two kernels for programs that read coefficients from device memory (stpde_res_coefs) ----------------
+// A block belongs to ONE batch element (grid (ceil(N / 256), B)), so the coefficient values a point sees are uniform over the
+// block: thread k stages value[k][per_batch[k] ? b : 0] into LDS next to the program, and a late-bound CONST (b != 0) reads
+// coef[a].  The values are read at run time: an in-place update of a coefficient tensor is seen by the next launch (and by the
+// next replay of a graph that captured it).
+struct CoefArgs {
+  int n, N, det;
+  int per_batch[STPDE_RES_MAX_COEF];
+  const float* value[STPDE_RES_MAX_COEF];
+  float* bar[STPDE_RES_MAX_COEF];
+};
+
+__device__ __forceinline__ void res_stage_coefs(const CoefArgs& c, int b, float* coef) {
+#pragma unroll
+  for (int k = 0; k < STPDE_RES_MAX_COEF; ++k)
+    if ((int)threadIdx.x == k) coef[k] = k < c.n ? c.value[k][c.per_batch[k] ? b : 0] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void k_residual_coef_fwd(ResArgs a, CoefArgs c) {
+  __shared__ stpde_res_ins prog[RES_MAX];
+  __shared__ float coef[STPDE_RES_MAX_COEF];
+  for (int i = threadIdx.x; i < a.nins; i += 256) prog[i] = a.prog[i];
+  res_stage_coefs(c, blockIdx.y, coef);
+  __syncthreads();
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= c.N) return;
+  const int p = blockIdx.y * c.N + q;
+  float v[RES_MAX];
+  for (int i = 0; i < a.nins; ++i) {
+    const stpde_res_ins in = prog[i];
+    v[i] = res_eval<true>(in, v, a, p, coef);
+    if (in.op == STPDE_RES_OUT) a.res[(size_t)in.b * a.P + p] = v[i];
+  }
+}
+
+// The adjoint: value replay and reverse sweep as k_residual_bwd (jets_bar is owned per point).  The adjoint register of a
+// late-bound CONST is d loss / d coefficient AT this point; where a gradient is wanted (bar[k] != NULL) it is summed over the
+// block -- wave_sum, four partials in LDS, (p0 + p1) + (p2 + p3): the shape of k_loss_sum -- and one thread adds the block sum
+// into bar[k][per_batch[k] ? b : 0] (fp32 atomic, or the long accumulator in deterministic mode).  The program is uniform over
+// the block, so every thread reaches that reduction at the same instruction.  No thread leaves early: the lanes past the
+// batch element's last point (live == false) run neither the replay nor the rules -- no load, no store -- and enter every
+// reduction with exactly +0.
+__global__ __launch_bounds__(256) void k_residual_coef_bwd(ResArgs a, CoefArgs c) {
+  __shared__ stpde_res_ins prog[RES_MAX];
+  __shared__ float coef[STPDE_RES_MAX_COEF];
+  __shared__ float* cbar[STPDE_RES_MAX_COEF];
+  __shared__ float part[4];
+  for (int i = threadIdx.x; i < a.nins; i += 256) prog[i] = a.prog[i];
+  res_stage_coefs(c, blockIdx.y, coef);
+#pragma unroll
+  for (int k = 0; k < STPDE_RES_MAX_COEF; ++k)
+    if ((int)threadIdx.x == k)      // (a null bar[k] stays null: no gradient wanted; a long accumulator is 2 * STPDE_DET_K floats)
+      cbar[k] = (k < c.n && c.bar[k]) ? c.bar[k] + (c.per_batch[k] ? (size_t)blockIdx.y * (c.det ? 2 * STPDE_DET_K : 1) : 0) : nullptr;
+  __syncthreads();
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  const bool live = q < c.N;
+  const int p = blockIdx.y * c.N + (live ? q : 0);
+  float v[RES_MAX], g[RES_MAX];
+  if (live) {
+    for (int i = 0; i < a.nins; ++i) {
+      v[i] = res_eval<true>(prog[i], v, a, p, coef);
+      g[i] = 0.f;
+    }
+  }
+  for (int i = a.nins - 1; i >= 0; --i) {
+    const stpde_res_ins in = prog[i];
+    if (in.op == STPDE_RES_CONST && in.b != 0) {          // uniform over the block
+      float* dst = cbar[in.a & (STPDE_RES_MAX_COEF - 1)];
+      if (dst) {                                           // uniform as well
+        float gi = 0.f;
+        if (live) gi = g[i];
+        const float s = wave_sum(gi);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) acc_add_f32(dst, 0, (part[0] + part[1]) + (part[2] + part[3]), c.det);
+        __syncthreads();                                   // part is written again by the next coefficient
+      }
       continue;
     }
-    switch (in.op) {
-      case STPDE_RES_OUT: g[in.a] += a.res_bar[(size_t)in.b * a.P + p]; break;
-      case STPDE_RES_JET: {
-        float* dst = a.jets_bar + (size_t)in.a * a.ld_s + (size_t)in.b * a.ld_c + p;   // this thread owns point p
-        *dst += gi;
-        break;
-      }
-      case STPDE_RES_ADD: g[in.a] += gi; g[in.b] += gi; break;
-      case STPDE_RES_SUB: g[in.a] += gi; g[in.b] -= gi; break;
-      case STPDE_RES_MUL: g[in.a] += gi * v[in.b]; g[in.b] += gi * v[in.a]; break;
-      case STPDE_RES_DIV: g[in.a] += gi / v[in.b]; g[in.b] -= gi * v[i] / v[in.b]; break;
-      case STPDE_RES_NEG: g[in.a] -= gi; break;
-      case STPDE_RES_POWI:   // d(x^n)/dx = n x^(n-1), evaluated without dividing by x (x = 0 is a regular point for n >= 1)
-        if (in.b != 0) g[in.a] += gi * (float)in.b * res_ipow(v[in.a], in.b - 1);
-        break;
-      case STPDE_RES_SIN: g[in.a] += gi * cosf(v[in.a]); break;
-      case STPDE_RES_COS: g[in.a] -= gi * sinf(v[in.a]); break;
-      case STPDE_RES_EXP: g[in.a] += gi * v[i]; break;
-      case STPDE_RES_LOG: g[in.a] += gi / v[in.a]; break;
-      case STPDE_RES_SQRT: g[in.a] += gi * 0.5f / v[i]; break;
-      case STPDE_RES_TANH: g[in.a] += gi * (1.f - v[i] * v[i]); break;
-      case STPDE_RES_ABS: g[in.a] += v[in.a] > 0.f ? gi : (v[in.a] < 0.f ? -gi : 0.f); break;   // torch: sign(0) = 0
-      default: break;   // X, CONST: the coordinates are not differentiated on this path
-    }
+    if (live) res_bwd_step(in, i, v, g, a, p);
   }
 }
 
@@ -241,6 +332,70 @@ extern "C" int stpde_residual_bwd(const stpde_res_ins* prog_dev, int nins, int n
   ResArgs a{prog_dev, nins, n_eq, n_out, P, jets, ld_stream, ld_channel, x, nullptr, res_bar, jets_bar};
   STPDE_LAUNCH(k_residual_bwd, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
   return stpde_check_launch("k_residual_bwd");
+}
+
+static int res_coef_check(const stpde_res_coefs* coefs, int P, CoefArgs* c) {
+  if (!coefs) {
+    stpde_set_error("residual_coef: null stpde_res_coefs");
+    return STPDE_E_BADARG;
+  }
+  if (coefs->n < 1 || coefs->n > STPDE_RES_MAX_COEF) {
+    stpde_set_error("residual_coef: %d coefficients (1 .. %d)", coefs->n, STPDE_RES_MAX_COEF);
+    return STPDE_E_BADARG;
+  }
+  if (coefs->n_per_batch <= 0 || P % coefs->n_per_batch != 0 || P / coefs->n_per_batch > 65535) {
+    stpde_set_error("residual_coef: P = %d points are not B * n_per_batch with n_per_batch = %d (B <= 65535)", P,
+                    coefs->n_per_batch);
+    return STPDE_E_BADARG;
+  }
+  c->n = coefs->n;
+  c->N = coefs->n_per_batch;
+  c->det = coefs->det ? 1 : 0;
+  for (int k = 0; k < STPDE_RES_MAX_COEF; ++k) {
+    const bool used = k < coefs->n;
+    if (used && !coefs->value[k]) {
+      stpde_set_error("residual_coef: value[%d] is null", k);
+      return STPDE_E_BADARG;
+    }
+    c->per_batch[k] = used && coefs->per_batch[k] ? 1 : 0;
+    c->value[k] = used ? coefs->value[k] : nullptr;
+    c->bar[k] = used ? coefs->bar[k] : nullptr;
+  }
+  return STPDE_OK;
+}
+
+extern "C" int stpde_residual_coef_fwd(const stpde_res_ins* prog_dev, int nins, int n_eq, int n_out, int P,
+                                       const float* jets, long ld_stream, long ld_channel, const float* x, float* res,
+                                       const stpde_res_coefs* coefs, void* stream) {
+  int rc = res_check(prog_dev, nins, n_eq, n_out, P, jets);
+  if (rc) return rc;
+  if (!res) {
+    stpde_set_error("residual_coef_fwd: null output");
+    return STPDE_E_BADARG;
+  }
+  CoefArgs c;
+  rc = res_coef_check(coefs, P, &c);
+  if (rc) return rc;
+  ResArgs a{prog_dev, nins, n_eq, n_out, P, jets, ld_stream, ld_channel, x, res, nullptr, nullptr};
+  STPDE_LAUNCH(k_residual_coef_fwd, dim3((c.N + 255) / 256, P / c.N), dim3(256), 0, (hipStream_t)stream, a, c);
+  return stpde_check_launch("k_residual_coef_fwd");
+}
+
+extern "C" int stpde_residual_coef_bwd(const stpde_res_ins* prog_dev, int nins, int n_eq, int n_out, int P,
+                                       const float* jets, long ld_stream, long ld_channel, const float* x,
+                                       const float* res_bar, float* jets_bar, const stpde_res_coefs* coefs, void* stream) {
+  int rc = res_check(prog_dev, nins, n_eq, n_out, P, jets);
+  if (rc) return rc;
+  if (!res_bar || !jets_bar) {
+    stpde_set_error("residual_coef_bwd: null pointer");
+    return STPDE_E_BADARG;
+  }
+  CoefArgs c;
+  rc = res_coef_check(coefs, P, &c);
+  if (rc) return rc;
+  ResArgs a{prog_dev, nins, n_eq, n_out, P, jets, ld_stream, ld_channel, x, nullptr, res_bar, jets_bar};
+  STPDE_LAUNCH(k_residual_coef_bwd, dim3((c.N + 255) / 256, P / c.N), dim3(256), 0, (hipStream_t)stream, a, c);
+  return stpde_check_launch("k_residual_coef_bwd");
 }
 
 // ---- loss reductions of the train step (experiments/rb2d/train.py:69-76: l1 / mse / smooth_l1 of prediction vs target

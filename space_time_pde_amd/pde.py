@@ -28,9 +28,15 @@ holds), ``Heaviside(a, h0)`` and the constants pi, E, EulerGamma, GoldenRatio, C
 
 Coefficients (an extension of the reference surface): ``PDELayer(in_vars, out_vars, param_vars='nu')`` declares symbols whose
 values are tensors handed over with ``update_parameters`` -- one value for all points or one per batch element, optionally
-requiring grad (inverse problems, mixed-regime batches).  Both torch strategies take them.  The HIP residual evaluator does
-not: with the HIP jets the residual algebra of such a layer is evaluated by the lambdified torch functions (counted and
-reported once as ``residual_torch_fallbacks``).
+requiring grad (inverse problems, mixed-regime batches).  Both torch strategies take them.  With the HIP jets the residual
+algebra of such a layer is by default evaluated by the lambdified torch functions (counted and reported once as
+``residual_torch_fallbacks``).  ``PDELayer(..., device_params=True)`` hands it to the HIP residual evaluator instead: a
+coefficient compiles to a late-bound CONST (no new opcode: ``_compile_residual_program(..., coef_slots=)``), the kernels
+``k_residual_coef_fwd`` / ``_bwd`` read the tensors when they run -- an in-place update is seen by the next call and by the next
+replay of a ``train_step.GraphedStep`` -- and the backward sums the coefficient gradients inside its one launch (long
+accumulators in deterministic mode).  A coefficient computed from a leaf (``nu = exp(log_nu)``) works through autograd.  The
+torch functions still take over, counted as before, for more than 8 coefficients, a coefficient that is not fp32, query points
+that are not [B, N, n_in], and a program beyond 192 instructions.
 """
 import ctypes as C
 
@@ -225,7 +231,7 @@ class _Unsupported(Exception):
     pass
 
 
-def _compile_residual_program(exprs, in_vars, sym_to_slot, extended=False, conditional=False):
+def _compile_residual_program(exprs, in_vars, sym_to_slot, extended=False, conditional=False, coef_slots=None):
     """Straight-line SSA program (common sub-expressions shared) for a list of sympy expressions.
 
     sym_to_slot: {sympy symbol: (stream, channel)} for the jet atoms.  Returns (numpy program, uses_x) or None when
@@ -234,8 +240,12 @@ def _compile_residual_program(exprs, in_vars, sym_to_slot, extended=False, condi
     and expression exponents, tan sinh cosh asin acos atan atan2).  conditional (with extended): also use LT .. STEPC,
     for what extended alone rejects (Piecewise over relationals joined by And / Or / Not as a chain of selects on float masks;
     Heaviside with another H(0); pi, E, EulerGamma, GoldenRatio and Catalan as fp32 constants, as an exponent too).  What
-    compiles without a switch compiles to the same bytes with it."""
-    ins, memo, uses_x = [], {}, [False]
+    compiles without a switch compiles to the same bytes with it.
+
+    coef_slots: {sympy symbol: k} for coefficients whose values the device reads from tensors (stpde_residual_coef_fwd / _bwd).
+    Such a symbol compiles to ONE late-bound CONST (a = k, b = 1, c = 0; every other CONST has a = b = 0), and the return value
+    becomes (program, uses_x, the sorted k the program reads).  None: nothing changes."""
+    ins, memo, uses_x, used_coefs = [], {}, [False], set()
 
     def emit(op, a=0, b=0, c=0.0):
         ins.append((_RES_OPS[op], int(a), int(b), float(c)))
@@ -314,6 +324,9 @@ def _compile_residual_program(exprs, in_vars, sym_to_slot, extended=False, condi
             elif e in in_vars:
                 uses_x[0] = True
                 idx = emit("X", in_vars.index(e))
+            elif coef_slots is not None and e in coef_slots:
+                used_coefs.add(int(coef_slots[e]))
+                idx = emit("CONST", coef_slots[e], 1)
             else:
                 raise _Unsupported(e)
         elif e.is_Number:
@@ -376,6 +389,8 @@ def _compile_residual_program(exprs, in_vars, sym_to_slot, extended=False, condi
         return None
     if len(ins) > _RES_MAX_INS:
         return None
+    if coef_slots is not None:
+        return np.array(ins, dtype=_RES_DT), uses_x[0], sorted(used_coefs)
     return np.array(ins, dtype=_RES_DT), uses_x[0]
 
 
@@ -418,23 +433,100 @@ class _ResidualHip(torch.autograd.Function):
         jets, x2d, prog_t = ctx.saved_tensors
         nins, n_eq = ctx.meta
         P, n_out = jets.shape[2], jets.shape[1]
-        # jets may be the slice [:, :, :P] of a buffer whose rows are padded (lig_jet.lig_jets at an odd point count), and the
-        # kernel addresses jets_bar with the strides of jets: one zero-filled block of that extent, viewed the same way
-        # (zeros_like would return dense strides for such a slice)
-        extent = (jets.shape[0] - 1) * jets.stride(0) + (n_out - 1) * jets.stride(1) + P
-        jbar = torch.zeros(extent, device=jets.device, dtype=jets.dtype).as_strided(jets.shape, jets.stride())
+        jbar = _jets_bar_like(jets)
         _lib.check(L.stpde_residual_bwd(_lib.ptr(prog_t), nins, n_eq, n_out, P, _lib.ptr(jets), jets.stride(0),
                                         jets.stride(1), _lib.ptr(x2d), _lib.ptr(gres.contiguous()), _lib.ptr(jbar),
                                         _lib.stream_ptr()))
         return jbar, None, None, None, None
 
 
+def _jets_bar_like(jets):
+    """The zero-filled jets_bar of a residual backward.  jets may be the slice [:, :, :P] of a buffer whose rows are padded
+    (lig_jet.lig_jets at an odd point count), and the kernels address jets_bar with the strides of jets: one zero-filled block of
+    that extent, viewed the same way (zeros_like would return dense strides for such a slice)."""
+    extent = (jets.shape[0] - 1) * jets.stride(0) + (jets.shape[1] - 1) * jets.stride(1) + jets.shape[2]
+    return torch.zeros(extent, device=jets.device, dtype=jets.dtype).as_strided(jets.shape, jets.stride())
+
+
+class _ResidualCoefHip(torch.autograd.Function):
+    """_ResidualHip for a program with late-bound CONSTs: ``coefs`` are the tensors the program reads (fp32, contiguous, on the
+    device of the jets, [] / [1] / [B]), ``ks`` their coefficient indices.  backward returns d loss / d jets and, for every
+    coefficient that wants one, its gradient in the tensor's own shape -- summed over the points inside the kernel."""
+
+    @staticmethod
+    def _record(coefs, ks, n_batch, P, bars=None):
+        rec = _lib.ResCoefs()
+        rec.n = max(ks) + 1
+        rec.n_per_batch = P // n_batch
+        rec.det = 1 if (bars is not None and _lib.deterministic) else 0
+        for j, (k, t) in enumerate(zip(ks, coefs)):
+            rec.per_batch[k] = 1 if t.numel() != 1 else 0
+            rec.value[k] = t.data_ptr()
+            if bars is not None and bars[j] is not None:
+                rec.bar[k] = bars[j].data_ptr()
+        for k in range(rec.n):          # an index the program does not read: any valid address (it is never dereferenced per point)
+            if not rec.value[k]:
+                rec.value[k] = coefs[0].data_ptr()
+        return rec
+
+    @staticmethod
+    @_lib.guarded
+    def forward(ctx, jets, x2d, prog_t, nins, n_eq, n_batch, ks, *coefs):
+        L = _lib.lib()
+        P, n_out = jets.shape[2], jets.shape[1]
+        if not (jets.stride(2) == 1 and jets.stride(1) >= P and jets.stride(0) >= (n_out - 1) * jets.stride(1) + P):
+            jets = jets.contiguous()
+        res = torch.empty(n_eq, P, device=jets.device, dtype=torch.float32)
+        rec = _ResidualCoefHip._record(coefs, ks, n_batch, P)
+        _lib.check(L.stpde_residual_coef_fwd(_lib.ptr(prog_t), nins, n_eq, n_out, P, _lib.ptr(jets), jets.stride(0),
+                                             jets.stride(1), _lib.ptr(x2d), _lib.ptr(res), C.byref(rec), _lib.stream_ptr()))
+        ctx.save_for_backward(jets, x2d, prog_t, *coefs)
+        ctx.meta = (nins, n_eq, n_batch, ks)
+        return res
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    @_lib.guarded
+    def backward(ctx, gres):
+        L = _lib.lib()
+        jets, x2d, prog_t = ctx.saved_tensors[:3]
+        coefs = ctx.saved_tensors[3:]
+        nins, n_eq, n_batch, ks = ctx.meta
+        P, n_out = jets.shape[2], jets.shape[1]
+        jbar = _jets_bar_like(jets)
+        want = ctx.needs_input_grad[7:]
+        det = _lib.deterministic
+        per = 2 * _lib.DET_K if det else 1            # floats of storage per gradient element
+        sizes = [t.numel() if w else 0 for t, w in zip(coefs, want)]
+        acc = torch.zeros(max(1, sum(sizes)) * per, device=jets.device, dtype=torch.float32)
+        bars, o = [], 0
+        for n in sizes:
+            bars.append(acc[o * per:(o + n) * per] if n else None)
+            o += n
+        rec = _ResidualCoefHip._record(coefs, ks, n_batch, P, bars)
+        _lib.check(L.stpde_residual_coef_bwd(_lib.ptr(prog_t), nins, n_eq, n_out, P, _lib.ptr(jets), jets.stride(0),
+                                             jets.stride(1), _lib.ptr(x2d), _lib.ptr(gres.contiguous()), _lib.ptr(jbar),
+                                             C.byref(rec), _lib.stream_ptr()))
+        if det and o:       # the long accumulators -> fp32 (train_step._LossSumHip's pattern)
+            out = torch.empty(o, device=jets.device, dtype=torch.float32)
+            _lib.check(L.stpde_det_finalize(_lib.ptr(acc), o, _lib.ptr(out), _lib.stream_ptr()))
+            acc, per = out, 1
+        grads, o = [], 0
+        for t, n in zip(coefs, sizes):
+            grads.append(acc[o:o + n].reshape(t.shape) if n else None)
+            o += n
+        return (jbar, None, None, None, None, None, None) + tuple(grads)
+
+
 class PDELayer(object):
     """PDE Layer for querying values and computing PDE residues."""
 
-    def __init__(self, in_vars, out_vars, param_vars=''):
+    def __init__(self, in_vars, out_vars, param_vars='', device_params=False):
         """in_vars / out_vars: strings of variable names, e.g. 'x, y, t' and 'u, v, p'; param_vars: names of coefficient
-        symbols (e.g. 'nu' or 'Ra, Pr') whose values ``update_parameters`` sets."""
+        symbols (e.g. 'nu' or 'Ra, Pr') whose values ``update_parameters`` sets; device_params: with the HIP jets, evaluate the
+        residuals of a layer with coefficients in the HIP residual kernels too, which then read the coefficient tensors (off: the
+        lambdified torch functions evaluate them)."""
+        self.device_params = bool(device_params)
         self.in_vars = sympy.symbols(in_vars)
         self.out_vars = sympy.symbols(out_vars)
         self.param_vars = sympy.symbols(param_vars) if param_vars.strip() else ()
@@ -453,6 +545,7 @@ class PDELayer(object):
         self.eqns_jet = {}   # _JetProgram or None per equation
         self._combo = False  # lazily built combined-second-order plan (False = not built yet)
         self._res_progs = {}  # {(stream layout key): compiled device residual program or None}
+        self._res_coefs = {}  # {(stream layout key): the coefficient indices that program reads}
         self.forward_method = None
 
     # ------------------------------------------------------------------------------------------------
@@ -480,6 +573,7 @@ class PDELayer(object):
         self.eqns_jet.update({eqn_name: self._compile_jet(expr)})
         self._combo = False   # combined-second-order plan is rebuilt lazily
         self._res_progs = {}
+        self._res_coefs = {}
 
     def _combo_plan(self):
         """If every equation is LINEAR in the second derivatives and uses them only through one common combination
@@ -703,14 +797,18 @@ class PDELayer(object):
 
         return {name: prog.fn(*(cols + [atom(k) for k in prog.atoms])) for name, prog in progs.items()}
 
-    def _residues_hip(self, x, jets, progs, stream_of, shape):
-        """All residuals of all equations in ONE HIP kernel (and one for the backward) instead of ~100 elementwise
-        torch kernels; None when an equation uses something the device evaluator does not implement."""
-        if not (jets.is_cuda and jets.dtype == torch.float32 and all(p.expr is not None for p in progs.values())):
+    def _coef_slots(self):
+        """{coefficient symbol: k} for the device programs of a layer with ``device_params``; None when the layer has none to
+        offer (the flag is off, or more coefficients than the kernels stage)."""
+        if not (self.device_params and self.param_vars) or len(self.param_vars) > _lib.RES_MAX_COEF:
             return None
-        if self.param_vars:
-            return None     # coefficients in tensors: the device evaluator reads constants only
-        key = (tuple(sorted((str(k), v) for k, v in stream_of.items())), str(jets.device))
+        return {s: k for k, s in enumerate(self.param_vars)}
+
+    def _res_program(self, progs, stream_of, device):
+        """The device program of these equations for this stream layout, compiled once and kept on ``device``: (program tensor,
+        instructions, uses_x) or None when the device evaluator cannot take them; the coefficient indices it reads are kept
+        beside it in ``_res_coefs``."""
+        key = (tuple(sorted((str(k), v) for k, v in stream_of.items())), str(device))
         ent = self._res_progs.get(key, False)
         if ent is False:
             slots = {}
@@ -718,19 +816,57 @@ class PDELayer(object):
                 for akey, sym in prog.syms.items():
                     slots[sym] = (stream_of[akey[1]], akey[0])
             comp = _compile_residual_program([p.expr for p in progs.values()], list(self.in_vars), slots, extended=True,
-                                             conditional=True)
+                                             conditional=True, coef_slots=self._coef_slots())
             ent = None
             if comp is not None:
-                arr, uses_x = comp
-                ent = (torch.from_numpy(arr.view(np.uint8).copy()).to(jets.device), len(arr), uses_x)
+                arr, uses_x = comp[:2]
+                ent = (torch.from_numpy(arr.view(np.uint8).copy()).to(device), len(arr), uses_x)
+                self._res_coefs[key] = tuple(comp[2]) if len(comp) > 2 else ()
             self._res_progs[key] = ent
+        return ent if ent is None else ent + (self._res_coefs[key],)
+
+    def device_program_compiles(self, device="cpu"):
+        """Whether the HIP residual evaluator takes this layer's equations, coefficients included (``device_params``), in the
+        stream layout its own jet request asks for."""
+        progs = self.eqns_jet
+        if not (progs and all(p is not None and p.expr is not None for p in progs.values())):
+            return False
+        stream_of = {(): 0, (0,): 1, (1,): 2, (2,): 3}
+        plan = self._combo_plan() if self.n_in == 3 else None
+        if plan is not None:
+            stream_of[("L",)] = 4
+            progs = plan["progs"]
+        else:
+            pairs = sorted({mi for p in progs.values() for _, mi in p.atoms if len(mi) == 2})
+            for k, pr in enumerate(pairs):
+                stream_of[pr] = 4 + k
+        return self._res_program(progs, stream_of, device) is not None
+
+    def _residues_hip(self, x, jets, progs, stream_of, shape):
+        """All residuals of all equations in ONE HIP kernel (and one for the backward) instead of ~100 elementwise
+        torch kernels; None when an equation uses something the device evaluator does not implement."""
+        if not (jets.is_cuda and jets.dtype == torch.float32 and all(p.expr is not None for p in progs.values())):
+            return None
+        if self.param_vars and not (self.device_params and x.dim() == 3):
+            return None     # coefficients in tensors: the device evaluator reads them for a layer with device_params only
+        ent = self._res_program(progs, stream_of, jets.device)
         if ent is None:
             return None
-        prog_t, nins, uses_x = ent
+        prog_t, nins, uses_x, ks = ent
+        coefs = []
+        if ks:
+            vals = self._param_values(x)
+            coefs = [vals[k].to(jets.device) for k in ks]
+            if not all(t.dtype == torch.float32 for t in coefs):
+                return None
+            coefs = [t.contiguous() for t in coefs]
         x2d = x.detach().reshape(-1, self.n_in).contiguous().float() if uses_x else None
         if x2d is not None and self.n_in < 3:      # the evaluator addresses x as [P][3]
             x2d = torch.nn.functional.pad(x2d, (0, 3 - self.n_in)).contiguous()
-        res = _ResidualHip.apply(jets, x2d, prog_t, nins, len(progs))
+        if ks:      # (a declared coefficient that no equation uses is not handed over: its .grad stays None)
+            res = _ResidualCoefHip.apply(jets, x2d, prog_t, nins, len(progs), x.shape[0], ks, *coefs)
+        else:
+            res = _ResidualHip.apply(jets, x2d, prog_t, nins, len(progs))
         return {name: res[k].reshape(shape) for k, name in enumerate(progs)}
 
     def __call__(self, x, return_residue=True):

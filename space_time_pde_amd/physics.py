@@ -28,11 +28,12 @@ def _transport(q, nt, nx, nz, diffusivity, source):
 
 
 def get_rb2_pde_layer(mean=None, std=None, t_crop=2., z_crop=1., x_crop=2., prandtl=1., rayleigh=1e6,
-                      use_continuity=False):
+                      use_continuity=False, device_params=False):
     """PDE layer for the RB2 governing equations; forward method still has to be set by the caller.
 
     mean/std: per-channel (p, b, u, w) normalisation constants or None; when given, every channel v is replaced by
     v*std+mean inside and outside ``dif`` (change of variables, reference :38-56).
+    device_params: ``PDELayer(device_params=)`` -- with tensor coefficients, evaluate the residuals in the HIP kernels.
     """
     symbolic = torch.is_tensor(rayleigh) or torch.is_tensor(prandtl)
     if symbolic:
@@ -61,7 +62,8 @@ def get_rb2_pde_layer(mean=None, std=None, t_crop=2., z_crop=1., x_crop=2., pran
                 len(mean), len(std)))
         subs_dict = {v: '{}*{}+{}'.format(v, std[i], mean[i]) for i, v in enumerate(_OUT)}
 
-    layer = PDELayer(in_vars='t, x, z', out_vars=', '.join(_OUT), param_vars='Ra, Pr' if symbolic else '')
+    layer = PDELayer(in_vars='t, x, z', out_vars=', '.join(_OUT), param_vars='Ra, Pr' if symbolic else '',
+                     device_params=device_params)
     for name, eqn in equations:
         layer.add_equation(eqn, name, subs_dict=subs_dict)
     if symbolic:

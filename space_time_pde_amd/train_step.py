@@ -261,7 +261,12 @@ class GraphedStep:
     decisions of the step (memory plan, kernel variants) depend on shapes only and are frozen at capture.  So is the operand
     precision of the U-Net's 3x3x3 convolutions (``unet3d.conv_precision``): a graph keeps the mode it was captured with.
 
-    A layer with tensor coefficients (``PDELayer(param_vars=...)``) is refused: capturing them is not implemented.
+    A layer with tensor coefficients (``PDELayer(param_vars=...)``) is taken when the HIP residual kernels read them
+    (``device_params=True``), its equations compile for the device evaluator and every grad-requiring coefficient is a leaf on
+    the step's device: the kernels load the values at each replay, so an in-place update (an optimizer step, ``Ra.data.mul_``)
+    needs no re-capture, and the leaves join ``self.params`` -- their ``.grad`` is a static tensor like the network's and a
+    capturable optimizer may own them.  Any other layer with coefficients is refused (``NotImplementedError``), as before:
+    capturing the torch functions that evaluate them is not implemented.
 
     Inputs are copied into static buffers before each replay; ``.grad`` of every parameter is a static tensor of the graph's
     memory pool, rewritten by each replay (``self.grads`` keeps them).  Not for a distributed step (collectives are not captured
@@ -304,9 +309,21 @@ class GraphedStep:
                                  "as None")
             input_grid, point_coord, point_value = sampler.lres, sampler.point_coord, sampler.point_value
         self.sampler = sampler
+        coef_leaves = []
         if getattr(pde_layer, "param_vars", ()):
-            raise NotImplementedError("GraphedStep does not take a PDELayer with tensor coefficients (param_vars): use "
-                                      "sharded_step, or give the layer numbers")
+            vals = getattr(pde_layer, "params", None) or {}
+            if not getattr(pde_layer, "device_params", False):
+                raise NotImplementedError("GraphedStep takes a PDELayer with tensor coefficients (param_vars) only when the "
+                                          "HIP residual kernels read them: build the layer with device_params=True, use "
+                                          "sharded_step, or give the layer numbers")
+            if any(t.requires_grad and not t.is_leaf for t in vals.values()):
+                raise NotImplementedError("GraphedStep (device_params=True): a grad-requiring equation coefficient must be a "
+                                          "leaf tensor, whose .grad the graph can own")
+            if not pde_layer.device_program_compiles():
+                raise NotImplementedError("GraphedStep (device_params=True): the HIP residual evaluator does not take this "
+                                          "layer's equations (its coefficients would be evaluated by torch functions): use "
+                                          "sharded_step")
+            coef_leaves = _coefficient_leaves(pde_layer)
         if optimizer is not None and not (getattr(optimizer, "capturable", False) and all(
                 hasattr(optimizer, m) for m in ("prepare", "state_tensors", "sync_lr", "flush_tables"))):
             raise ValueError("GraphedStep(optimizer=...) needs a capturable optimizer of this package (FusedClipAdam / "
@@ -315,7 +332,10 @@ class GraphedStep:
         if not input_grid.is_cuda:
             raise RuntimeError("GraphedStep needs CUDA/HIP tensors")
         self.optimizer = optimizer
-        self.params = [p for m in (unet, imnet) for p in m.parameters()]
+        if any(t.device != input_grid.device for t in coef_leaves):
+            raise NotImplementedError("GraphedStep (device_params=True): a grad-requiring equation coefficient must live on the "
+                                      "step's device (%s)" % (input_grid.device,))
+        self.params = [p for m in (unet, imnet) for p in m.parameters()] + coef_leaves
         snapshot = None
         if optimizer is not None:
             optimizer.prepare()

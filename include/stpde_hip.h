@@ -77,6 +77,10 @@ int stpde_last_error(char* buf, unsigned long n);
  * the MFMAs (no transposes through the LDS patch), and waves 4 .. 7 build their ring slot before their MFMAs instead of behind
  * them; the lock-step loop restores the old load form for all waves.  The results are the same bits either way (A/B timing,
  * tests/test_gpu_wgrad_fp32_phase_swap.py).
+ * "fc2_bwd_fused": exact fp32, second hidden layer of the reference width: 0 / 1 = a call of stpde_lig_imnet_jet_bwd that asks
+ * for it (STPDE_F_FC2_FUSED) and for weight gradients runs the layer's weight gradient and input gradient as ONE kernel
+ * (stpde_jet_fc2_bwd) where stpde_jet_fc2_bwd_supported says so; 2 = the two kernels whatever the call asks for.  Same bits
+ * either way in deterministic mode (tests/test_gpu_fc2_bwd_fused.py).
  * Returns the previous value, -1 for an unknown key.  Process-wide, thread-safe. */
 #define STPDE_TUNE_CONV3_LDS_OFF 0
 #define STPDE_TUNE_CONV3_LDS_MINBLK 1
@@ -84,7 +88,8 @@ int stpde_last_error(char* buf, unsigned long n);
 #define STPDE_TUNE_CONV_WGRAD_LDS_GX 3
 #define STPDE_TUNE_CONV1_WGRAD_LDS_GX 4
 #define STPDE_TUNE_WGRAD_FP32_SWAP 5
-#define STPDE_TUNE_COUNT 6
+#define STPDE_TUNE_FC2_BWD_FUSED 6
+#define STPDE_TUNE_COUNT 7
 int stpde_tune(const char* name, int value);
 /* Dispatch trace (test / debugging facility; nothing in the reference corresponds to it): while enabled, every kernel
  * launch records which template instantiation it dispatched ("<kernel expression> @ <launcher with template
@@ -253,6 +258,19 @@ int stpde_jet_fc1_bwd(const stpde_layer_desc* d, const float* abar1, const void*
                       const float* tanc0, const float* cw, const float* X, float* abar0, float* abar0_tan, float* dW_aug,
                       float* act_param_bar, void* stream);
 
+/* Exact fp32, second hidden layer of the reference width: stpde_jet_wgrad + stpde_jet_layer_bwd of that layer in ONE call
+ * (csrc/jet_fc2_bwd.hip).  Both products are partitioned by the layer's INPUT k-tile, so one eight-wave workgroup per row tile
+ * reads the adjoint blocks abar2 and the stashed pre-activations pre1 of fc1's rows once and evaluates their activation jets
+ * once.  d: the description stpde_jet_wgrad takes for this layer (first_hidden = 0, KT = 16, MT = 8, mfma_bf16 = 0, packed = 0,
+ * S1 = 3, S2 = 0 or the combined stream; d->det as there).  abar2 [tile][S][8][256], pre1 [tile][S][16][256], X, cw as for the two
+ * calls it replaces; WhT_pack: the fp32 pack of W2h^T (stpde_jet_layer_bwd's); abar1 [tile][S][16][256] receives the adjoint of
+ * fc1's rows and MAY be pre1 itself (every block is read and later written by the same wave); dW_aug: fc2's block of the flat
+ * gradient buffer; act_param_bar as stpde_jet_layer_bwd.  In deterministic mode dW_aug and abar1 are the bits of the two calls.
+ * stpde_jet_fc2_bwd_supported(d) != 0 iff this call serves d (a pure function of d). */
+int stpde_jet_fc2_bwd_supported(const stpde_layer_desc* d);
+int stpde_jet_fc2_bwd(const stpde_layer_desc* d, const float* abar2, const float* WhT_pack, const float* pre1, const float* X,
+                      const float* cw, float* abar1, float* dW_aug, float* act_param_bar, void* stream);
+
 /* ---- a4: corner-weighted reduction (src/local_implicit_grid.py:59) on all streams ------------------
  * jets[(s*n_out + ch)*ldp + p] (ldp >= P lets a chunk of points write into a larger [S][n_out][Ptotal] array)
  * from out_pre[tile][S][1][64][4] (fc5 output) and coef; and its adjoint. */
@@ -364,6 +382,10 @@ typedef struct {
 /* backward: dW_flat addresses long accumulators (stpde_layer_desc.det): [sum of the layers' dW_aug elements][6] int64, layer l at
  * element offset dw_off[l]; bit-reproducible IM-NET weight gradients */
 #define STPDE_F_DET 1024
+/* exact fp32, one-call order with STPDE_F_WGRAD: run the second hidden layer's weight gradient and input gradient as ONE kernel
+ * (stpde_jet_fc2_bwd) where stpde_jet_fc2_bwd_supported serves the layer and stpde_tune("fc2_bwd_fused") is not 2.  Opt-in: a
+ * call without this bit keeps the two kernels.  Same bits either way with STPDE_F_DET. */
+#define STPDE_F_FC2_FUSED 2048
 /* cfg_mlp = streams the layer kernels carry, cfg_out = streams of `jets` (they differ for piecewise-linear activations,
  * see stpde_lig_reduce_fwd); jets points at the first point of the chunk inside [S_out][n_out][ldp]. */
 int stpde_lig_imnet_jet_fwd(const stpde_imnet_plan* plan, const stpde_jet_cfg* cfg_mlp, const stpde_jet_cfg* cfg_out,

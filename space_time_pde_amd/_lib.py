@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 # STPDE_LIB: load another build of the library (A/B timing of kernel variants on one box; never set by tests or the driver)
 LIB_PATH = os.environ.get("STPDE_LIB") or os.path.join(_HERE, "libstpde_hip.so")
-_SOURCES = ["jet_layer.hip", "jet_layer_s00.hip", "jet_layer_s03.hip", "jet_layer_s30.hip", "jet_layer_s31.hip", "jet_layer_s32.hip", "jet_layer_s34.hip", "jet_layer_s36.hip", "jet_tail.hip", "jet_wgrad.hip", "jet_wgrad_s00.hip", "jet_wgrad_s30.hip", "jet_wgrad_s31.hip", "jet_wgrad_s32.hip", "jet_wgrad_s34.hip", "jet_wgrad_s36.hip", "jet_fc1_bwd.hip", "lig_gather_reduce.hip", "lig_pipeline.hip", "interp_nd.hip", "conv3d.hip", "conv3d_fused.hip", "optim.hip", "residual.hip", "bn.hip", "resample.hip", "sampler.hip", "sampler_median.hip", "api.cpp"]
+_SOURCES = ["jet_layer.hip", "jet_layer_s00.hip", "jet_layer_s03.hip", "jet_layer_s30.hip", "jet_layer_s31.hip", "jet_layer_s32.hip", "jet_layer_s34.hip", "jet_layer_s36.hip", "jet_tail.hip", "jet_wgrad.hip", "jet_wgrad_s00.hip", "jet_wgrad_s30.hip", "jet_wgrad_s31.hip", "jet_wgrad_s32.hip", "jet_wgrad_s34.hip", "jet_wgrad_s36.hip", "jet_fc1_bwd.hip", "jet_fc2_bwd.hip", "lig_gather_reduce.hip", "lig_pipeline.hip", "interp_nd.hip", "conv3d.hip", "conv3d_fused.hip", "optim.hip", "residual.hip", "bn.hip", "resample.hip", "sampler.hip", "sampler_median.hip", "api.cpp"]
 # --offload-compress: the gfx950 code objects are stored zstd-compressed in the fat binary (the HIP runtime inflates them at
 # module load): libstpde_hip.so 68 MB -> ~1/4; the instruction bytes are the same (tools/check_dpp_hazard.py scans them)
 _HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics",
@@ -68,7 +68,7 @@ class LigWorkspace(C.Structure):        # stpde_lig_workspace
 
 
 F_STASH, F_VALUE_TILES, F_FUSED_TAIL, F_TAN0_ROWSUM, F_DETERMINISTIC, F_WGRAD, F_WGRAD_FP32 = 1, 2, 4, 8, 16, 32, 64
-F_PHASE_A, F_PHASE_B, F_NO_FC1_FUSED, F_DET = 128, 256, 512, 1024
+F_PHASE_A, F_PHASE_B, F_NO_FC1_FUSED, F_DET, F_FC2_FUSED = 128, 256, 512, 1024, 2048
 LOSS_DET = 16      # STPDE_LOSS_DET: stpde_loss_sum into a long accumulator
 
 
@@ -280,6 +280,8 @@ _SIGNATURES = {
     "stpde_jet_wgrad": ([C.POINTER(LayerDesc), C.c_int] + [_VP] * 7, C.c_int),
     "stpde_jet_fc1_bwd_supported": ([C.POINTER(LayerDesc)], C.c_int),
     "stpde_jet_fc1_bwd": ([C.POINTER(LayerDesc)] + [_VP] * 11, C.c_int),
+    "stpde_jet_fc2_bwd_supported": ([C.POINTER(LayerDesc)], C.c_int),
+    "stpde_jet_fc2_bwd": ([C.POINTER(LayerDesc)] + [_VP] * 9, C.c_int),
     "stpde_lig_reduce_fwd": ([C.POINTER(JetCfg), C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, C.c_long, _VP], C.c_int),
     "stpde_lig_reduce_bwd": ([C.POINTER(JetCfg), C.c_int, C.c_int, C.c_int, _VP, C.c_long, _VP, _VP, _VP], C.c_int),
     "stpde_lig_xbar_scatter": ([C.POINTER(XbarDesc), C.POINTER(_VP), C.POINTER(_VP), _VP, _VP, _VP], C.c_int),
@@ -377,7 +379,17 @@ def tune(name, value):
     prev = lib().stpde_tune(name.encode(), int(value))
     if prev < 0:
         raise KeyError(name)
+    _tune_values[name] = int(value)
     return prev
+
+
+_tune_values = {}     # what this module last set each key to (the library has a setter only; every key starts at 0)
+
+
+def tune_value(name):
+    """The value ``tune`` last gave a key (0: never set).  Needs no library: the call record of the LIG jet path reads the
+    "fc2_bwd_fused" switch through it (the per-kernel driver follows the switch the one-call entry point reads itself)."""
+    return _tune_values.get(name, 0)
 
 
 class tuned:

@@ -36,7 +36,7 @@ extern "C" int stpde_version(void) { return 316; }
 // force other values to reach the multi-block-per-workgroup and ragged-tail paths on volumes a test can afford.
 #include <atomic>
 static const char* const g_tune_names[STPDE_TUNE_COUNT] = {"conv3_lds_off", "conv3_lds_minblk", "conv3_lds_gx", "conv_wgrad_lds_gx",
-                                                           "conv1_wgrad_lds_gx", "wgrad_fp32_swap"};
+                                                           "conv1_wgrad_lds_gx", "wgrad_fp32_swap", "fc2_bwd_fused"};
 static std::atomic<int> g_tune[STPDE_TUNE_COUNT];
 int stpde_tune_get(int key) { return (key >= 0 && key < STPDE_TUNE_COUNT) ? g_tune[key].load(std::memory_order_relaxed) : 0; }
 extern "C" int stpde_tune(const char* name, int value) {

@@ -278,6 +278,23 @@ extern "C" int stpde_lig_imnet_jet_bwd(const stpde_imnet_plan* p, const stpde_je
                                dW_flat + aw * p->dw_off[1], act_param_bar, stream);
     });
   };
+  // exact fp32, reference width: weight gradient + input gradient of the second hidden layer in one kernel (jet_fc2_bwd.hip).
+  // One-call order only (the dgrad-first phases keep the two kernels), for a call that asks for it (STPDE_F_FC2_FUSED); decided
+  // once per call, from the plan, the flags and the "fc2_bwd_fused" switch of stpde_tune.  abar1 goes over pre[1] in place, as the input gradient's own kernel writes it.
+  const bool fc2_fused_on = [&]() -> bool {
+    if (!wgrad || dfirst || !(flags & STPDE_F_FC2_FUSED) || stpde_tune_get(STPDE_TUNE_FC2_BWD_FUSED) == 2) return false;
+    stpde_layer_desc d = layer_desc(nt, p, 2, cfg, p->mfma_bf16);      // (bf16 and "fp32x3" plans keep their own kernels)
+    d.packed = packed_flags(p, 2, 1);
+    return stpde_jet_fc2_bwd_supported(&d) != 0;
+  }();
+  auto fc2_fused = [&] {
+    stpde_layer_desc d = layer_desc(nt, p, 2, cfg, 0);
+    d.det = det;
+    seq([&] {
+      return stpde_jet_fc2_bwd(&d, abar[2], p->WhT[2], ws->pre[1], ws->X, ws->cw, abar[1], dW_flat + aw * p->dw_off[2],
+                               act_param_bar, stream);
+    });
+  };
   auto dlatent_part = [&] {
     if (!dlatent) return;
     stpde_xbar_desc xd{};
@@ -333,6 +350,10 @@ extern "C" int stpde_lig_imnet_jet_bwd(const stpde_imnet_plan* p, const stpde_je
   for (int l = NL - 1; l >= 1; --l) {
     if (l == 1 && fc1_fused_ok()) {
       fc1_fused();
+      continue;
+    }
+    if (l == 2 && fc2_fused_on) {
+      fc2_fused();
       continue;
     }
     if (wgrad) wgrad_l(l);

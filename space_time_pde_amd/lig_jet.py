@@ -437,6 +437,7 @@ class JetCall:
     wgrad_split: bool       # "fp32x3": weight gradients on the split operands too
     fused_tail: bool        # fc3 -> fc5 in one kernel where ``tail`` / a value-tile pass allows
     fc1_fused: bool         # bf16 mode: fused backward of the first hidden layer (STPDE_FC1_FUSED)
+    fc2_fused: bool         # exact fp32: fused backward of the second hidden layer where the library serves it (``fc2_fused``)
     nd_backward: bool       # dim = 1, 2, 4: the HIP training backward is allowed
     nd_jets: bool           # dim = 1, 2: coordinate derivatives in HIP are allowed (forward passes that need no gradient)
     nd_jet_backward: bool   # dim = 1, 2: ... and so is their training backward (only together with ``nd_jets``)
@@ -488,6 +489,7 @@ class JetCall:
                    chunk=max(mult, chunk_points // mult * mult), need_grad=bool(need_grad), det=bool(_lib.deterministic),
                    det_dlatent=bool(deterministic_dlatent), value_tiles=bool(value_tiles), tan0_rowsum=bool(tan0_rowsum),
                    wgrad_split=bool(wgrad_split), fused_tail=bool(fused_tail), fc1_fused=fc1_fused_enabled(),
+                   fc2_fused=fc2_fused_enabled(),
                    nd_backward=bool(nd_backward), nd_jets=bool(nd_jets),
                    nd_jet_backward=bool(nd_jets and nd_jet_backward),
                    pipeline=bool(use_pipeline and profile is None and dim == 3),
@@ -588,7 +590,8 @@ def _flags(call, need_grad, need_wgrad=True):
     """STPDE_F_* of the one-call entry points (the forward reads F_STASH, F_VALUE_TILES and F_FUSED_TAIL only)"""
     bits = ((need_grad, _lib.F_STASH), (call.value_tiles, _lib.F_VALUE_TILES), (call.fused_tail, _lib.F_FUSED_TAIL),
             (call.tan0_rowsum, _lib.F_TAN0_ROWSUM), (call.det_dlatent, _lib.F_DETERMINISTIC), (need_wgrad, _lib.F_WGRAD),
-            (not call.wgrad_split, _lib.F_WGRAD_FP32), (not call.fc1_fused, _lib.F_NO_FC1_FUSED), (call.det, _lib.F_DET))
+            (not call.wgrad_split, _lib.F_WGRAD_FP32), (not call.fc1_fused, _lib.F_NO_FC1_FUSED), (call.det, _lib.F_DET),
+            (call.fc2_fused, _lib.F_FC2_FUSED))
     return sum(bit for on, bit in bits if on)
 
 
@@ -889,6 +892,14 @@ def _backward_chunk(call, packs, packs16, saved, jets_bar, dw_flat, dlatent, pba
             with _timed("layer1_bwd"):
                 check(L.stpde_jet_fc1_bwd(C.byref(d), ptr(abar[1]), ptr(w16), ptr(z0), ptr(pv(packs, 0, "tanc")), ptr(cw),
                                           ptr(X), ptr(abar0), ptr(tan0), ptr(_dw_slice(call, dw_flat, 1)), ptr(pbar), st))
+            continue
+        if (l == 2 and need_wgrad and call.fc2_fused and not nd and w16 is None
+                and L.stpde_jet_fc2_bwd_supported(C.byref(dwg))):
+            # exact fp32, reference width: weight gradient + input gradient of the second hidden layer in ONE kernel
+            # (csrc/jet_fc2_bwd.hip: abar2 and the stash of fc1's rows read once, their activation jets evaluated once)
+            with _timed("layer2_bwd"):
+                check(L.stpde_jet_fc2_bwd(C.byref(dwg), ptr(abar[2]), ptr(pv(packs, 2, "WhT")), ptr(bufs[1]), ptr(X), ptr(cw),
+                                          ptr(abar[1]), ptr(_dw_slice(call, dw_flat, 2)), ptr(pbar), st))
             continue
         if need_wgrad:
             with _timed("layer%d_wgrad" % l):
@@ -1247,6 +1258,20 @@ def fc1_fused_enabled():
     STPDE_FC1_FUSED=0 (read once per call, by JetCall.make: tests switch it inside one process) runs the input gradient and the weight gradient of
     that layer as two kernels -- the A/B reference of tests/test_gpu_bf16_kernel_variants.py."""
     return os.environ.get("STPDE_FC1_FUSED", "1") != "0"
+
+
+# Exact fp32, reference width: fc2's weight gradient + input gradient as one kernel (csrc/jet_fc2_bwd.hip; same bits as the two
+# kernels in deterministic mode).  None = the caller's default: a direct jet call keeps the two kernels -- the instantiations the
+# parity fixtures of tests/test_gpu_reference_fixtures.py pin -- and the training step (train_step.sharded_step, what bench.py
+# times) turns it on for its own calls; True / False = for every call.  ``_lib.tune("fc2_bwd_fused", 2)`` overrides it: two kernels.
+fc2_fused = None
+
+
+def fc2_fused_enabled():
+    """``fc2_fused`` and the library switch, read once per call by JetCall.make; handed to the one-call entry point as
+    STPDE_F_FC2_FUSED and followed by the per-kernel driver, which names the launch ``layer2_bwd``."""
+    return bool(fc2_fused) and _lib.tune_value("fc2_bwd_fused") != 2
+
 
 DEFAULT_CHUNK = 1 << 20   # query points per launch chunk (per-chunk backward scratch: ~50 GB at 2^20; measured on
                           # MI355X: 2^17 / 2^18 / 2^19 / 2^20 points per chunk -> 459.8 / 458.7 / 455.5 / 454.3 ms per step)

@@ -135,10 +135,15 @@ def sharded_step(unet, imnet, pde_layer, input_grid, point_coord, point_value, n
     prev_deferred = getattr(unet, "deferred_weight_grads", None)
     if prev_deferred is not None:
         unet.deferred_weight_grads = os.environ.get("STPDE_UNET_DEFERRED", "1") != "0"
+    # ... and its jet call may take the fused backward of the second hidden layer (lig_jet.fc2_fused: None = this step decides)
+    prev_fc2 = lig_jet.fc2_fused
+    if prev_fc2 is None:
+        lig_jet.fc2_fused = True
     try:
         return _sharded_step(unet, imnet, pde_layer, input_grid, point_coord, point_value, n_points_global, alpha_reg,
                              alpha_pde, loss_type, xmin, xmax, distributed, sync_unet_grads)
     finally:
+        lig_jet.fc2_fused = prev_fc2
         if prev_deferred is not None:
             unet.deferred_weight_grads = prev_deferred
 

@@ -483,8 +483,9 @@ int stpde_lig_dlatent_reduce_nd(int D, int B, const int* n /* [D] on the host */
  * one forward pass: stpde_lig_gather_nd, stpde_lig_coef_nd, the layer kernels / stpde_jet_tail_fwd_p unchanged in a stream
  * set (3, 0), (3, 2), (3, 4) or (3, 6) over ntiles row tiles of 16 >> D points, stpde_lig_reduce_nd_jet_fwd.  The layer
  * kernels carry three tangent streams whatever D is: the caller's `tanc` packs must hold zeros for the columns d >= D, which
- * makes the streams of those axes identically zero.  Not served (the caller keeps the composed formulation): D = 4, the
- * combined second-order stream (its per-row weights are indexed two points per tile) and bf16 operands; the backward is below.
+ * makes the streams of those axes identically zero.  Not served (the caller keeps the composed formulation): D = 4 (by
+ * these two: it has entry points of its own, further below), the combined second-order stream (its per-row weights are
+ * indexed two points per tile) and bf16 operands; the backward is below.
  *   stpde_lig_coef_nd            coef[p][16] of stpde_lig_gather for point p of the chunk, from the same clip and cell index
  *                                as stpde_lig_gather_nd: {om[0][k], om[1][k], dom[0][k], dom[1][k], kap[k]} at 0 / 3 / 6 / 9 /
  *                                12 + k for k < D; om = 1, dom = 0, kap = 0 for the axes k >= D; entry 15 = 0.  Checks of
@@ -504,6 +505,40 @@ int stpde_lig_coef_nd(const stpde_gather_nd_desc* d, const float* pts, float* co
 int stpde_lig_reduce_nd_jet_fwd(const stpde_jet_cfg* cfg, int S_mlp, int D, int P, int ntiles, int n_out,
                                 const float* out_pre /* [ntiles][S_mlp][1][256] */, const float* coef,
                                 float* jets /* [S][n_out][ldp] */, long ldp, void* stream);
+
+/* ---- coordinate derivatives on 4-d grids (3-d space + time), forward only ------------------------------------------------
+ * The layer kernels carry three first-order streams; a 4-d grid has four axes.  A request runs as up to four PASSES over the one
+ * image of stpde_lig_gather_nd (one point = one 16-row tile): each pass is the layer kernels / stpde_jet_tail_fwd_p unchanged in
+ * a stream set (3, 0), (3, 2), (3, 4) or (3, 6) whose `tanc` packs hold the skip-block columns a0 < a1 < a2 of the pass's axis
+ * triple (slot i of the pass = axis a_i), followed by stpde_lig_reduce_nd4_jet_fwd.  Every mixed second derivative needs the
+ * first-order streams of its two axes only, and the four triples of {0, 1, 2, 3} hold all six mixed pairs.
+ *   stpde_lig_coef_nd4            coef[p][24] = {om[0][k], om[1][k], dom[0][k], dom[1][k], kap[k]} at 0 / 4 / 8 / 12 / 16 + k for
+ *                                 the four axes, entries 20 .. 23 = 0, from the same clip and cell index as stpde_lig_gather_nd.
+ *                                 Checks of stpde_lig_gather_nd, and D other than 4 refused.
+ *   stpde_lig_reduce_nd4_jet_fwd  the corner sum of one pass over the 16 corners, in corner order, with the terms of
+ *                                 stpde_lig_reduce_nd_jet_fwd: the weight is the product over all four axes, dw / d2w are taken
+ *                                 for the pass's axes.  Stream dst_value of jets receives the value, dst_first[i] the derivative
+ *                                 along axis[i], dst_pair[k] the second derivative along (pair0[k], pair1[k]); -1 = not stored.
+ *                                 A pass writes no other stream, so several passes fill one jets tensor.  S_mlp = 4 with
+ *                                 npairs > 0: the layer buffers hold no second-order streams (piecewise-linear activations),
+ *                                 they count as zero.  Refused with STPDE_E_BADARG: D other than 4; a null pointer; P < 1 or
+ *                                 P > ntiles or ntiles > P + 3; n_out outside 1..16; ldp < P; an axis triple that is not
+ *                                 strictly increasing inside 0..3; npairs other than 0, 2, 4, 6; S_mlp other than 4 and
+ *                                 4 + npairs; S outside 1..15; a pair axis outside the triple; a destination stream outside
+ *                                 [-1, S) or named twice.
+ * Nothing is read or written for p >= P; every index is bounded for every coordinate value (NaN, infinite, huge). */
+typedef struct {
+  int axis[3];             /* the pass's axis triple, strictly increasing, each < 4 */
+  int npairs;              /* S2 of the pass's stream set: 0, 2, 4 or 6 (padded by repeating a pair, destination -1) */
+  int pair0[6], pair1[6];  /* axes of pair k, both inside the triple */
+  int S_mlp;               /* streams of out_pre: 4 + npairs, or 4 */
+  int S;                   /* streams of the jets tensor */
+  int dst_value, dst_first[3], dst_pair[6]; /* stream of jets to write, or -1 */
+} stpde_nd4_pass_desc;
+int stpde_lig_coef_nd4(const stpde_gather_nd_desc* d, const float* pts, float* coef /* [P][24] */, void* stream);
+int stpde_lig_reduce_nd4_jet_fwd(const stpde_nd4_pass_desc* d, int D, int P, int ntiles, int n_out,
+                                 const float* out_pre /* [ntiles][S_mlp][1][256] */, const float* coef,
+                                 float* jets /* [S][n_out][ldp] */, long ldp, void* stream);
 
 /* ---- training through those derivatives (dim = 1, 2): the adjoint of stpde_lig_reduce_nd_jet_fwd ------------------------
  * Between stpde_lig_reduce_nd_jet_bwd and the d latent calls of the value path (stpde_lig_xbar_rows on the value-stream

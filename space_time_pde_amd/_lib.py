@@ -43,6 +43,11 @@ class GatherNdDesc(C.Structure):        # stpde_gather_nd_desc
                 ("cube", C.c_float * 4)]
 
 
+class Nd4PassDesc(C.Structure):         # stpde_nd4_pass_desc: one pass of a derivative request on a 4-d grid
+    _fields_ = [("axis", C.c_int * 3), ("npairs", C.c_int), ("pair0", C.c_int * 6), ("pair1", C.c_int * 6), ("S_mlp", C.c_int),
+                ("S", C.c_int), ("dst_value", C.c_int), ("dst_first", C.c_int * 3), ("dst_pair", C.c_int * 6)]
+
+
 class LayerDesc(C.Structure):
     _fields_ = [("ntiles", C.c_int), ("KT", C.c_int), ("MT", C.c_int), ("first_hidden", C.c_int), ("cfg", JetCfg),
                 ("mfma_bf16", C.c_int), ("packed", C.c_int), ("det", C.c_int)]
@@ -261,6 +266,9 @@ _SIGNATURES = {
     "stpde_lig_coef_nd": ([C.POINTER(GatherNdDesc), _VP, _VP, _VP], C.c_int),
     "stpde_lig_reduce_nd_jet_fwd": ([C.POINTER(JetCfg), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, C.c_long,
                                      _VP], C.c_int),
+    "stpde_lig_coef_nd4": ([C.POINTER(GatherNdDesc), _VP, _VP, _VP], C.c_int),
+    "stpde_lig_reduce_nd4_jet_fwd": ([C.POINTER(Nd4PassDesc), C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, C.c_long, _VP],
+                                     C.c_int),
     "stpde_lig_reduce_nd_jet_bwd": ([C.POINTER(JetCfg), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, C.c_long, _VP, _VP,
                                      _VP], C.c_int),
     "stpde_jet_wgrad_nd": ([C.POINTER(LayerDesc), C.c_int] + [_VP] * 6 + [C.c_int, _VP], C.c_int),

@@ -13,6 +13,8 @@
 //   k_reduce_nd / k_reduce_nd_bwd     D = 1, 2, 4: the value-only corner sum and its adjoint
 //   k_coef_nd<D> / k_reduce_nd_jet<D> D = 1, 2, forward only: the dim = 3 coefficient record per point and the corner sum of
 //                 every derivative stream over the 16 >> D points-per-tile rows
+//   k_coef_nd4 / k_reduce_nd4_jet     D = 4, forward only: the record of all four axes per point and the corner sum of one
+//                 PASS -- the (3, S2) layer sequence over one axis triple -- into the streams its destination map names
 //   k_xbar        d latent: xbar = sum_l W_s,l^T abar_l, scatter-added at the corner nodes or written per row (backward of the
 //                 advanced-index gather at src/regular_nd_grid_interpolation.py:65-66); dimension-agnostic
 // The geometry itself (clip, cell index, weights, relative coordinates, their jets) is written in interp_geom.h only.
@@ -1000,6 +1002,216 @@ extern "C" int stpde_lig_reduce_nd_jet_bwd(const stpde_jet_cfg* cfg, int S_mlp, 
   if (rc) return rc;
   ReduceNdJetBwdArgs a{*cfg, P, ntiles, n_out, S_mlp, ldp, jets_bar, coef, abar_out};
   return D == 1 ? launch_reduce_nd_jet_bwd<1>(a, (hipStream_t)stream) : launch_reduce_nd_jet_bwd<2>(a, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// coordinate derivatives on 4-d grids (3-d space + time), forward only.  The layer kernels carry three first-order streams, a
+// 4-d grid has four axes: a request runs as up to four PASSES, each the (3, S2) layer sequence over one axis triple (a0 < a1 <
+// a2) -- the caller's `tanc` packs of the pass hold the skip-block columns a0, a1, a2 -- over the ONE image of k_gather_nd<4>
+// (one point = one 16-row tile).  k_coef_nd4 writes the record of all four axes once per chunk; k_reduce_nd4_jet is the corner
+// sum of one pass: the weight is the product over all four axes, dw / ddw are taken for the pass's three axes, and a
+// destination-stream map says which stream of the caller's jets tensor the value, each first-order slot and each pair goes to
+// (-1: not stored), so that the passes of a request fill disjoint streams of one [1 + 4 + npairs][n_out][ldp] tensor.
+//
+// Addresses, bounded for EVERY input value -- NaN, infinite and huge coordinates included (tests/lig_nd4_jet_model.py restates
+// both bodies and records every index; tests/test_lig_nd4_jet_host.py runs them on such coordinates):
+//   k_coef_nd4        grid from P alone; p < P; pts p * 4 + k, k < 4; coef p * 24 + i, i < 24.  Nothing but pts is read: the
+//                     cell index point_cell() clamps forms no address here.
+//   k_reduce_nd4_jet  grid from P * n_out alone; p < P <= ntiles (one point per tile: checked on the host), ch < n_out <= 16.
+//                     coef   p * 24 + i, i < 24
+//                     src    tile = p < ntiles, stream s < S_mlp, lane = (ch >> 2) << 4 | corner < 64 (corner < 16), register
+//                            ch & 3: (p * S_mlp + s) * 256 + lane * 4 + (ch & 3) < ntiles * S_mlp * 256
+//                     dst    (t * n_out + ch) * ldp + p with t an entry of the destination map: -1 (skipped) or 0 <= t < S
+//                            (checked on the host), p < P <= ldp
+//                     No index depends on a value read from memory: axes, pairs and the destination map come from the
+//                     descriptor and are checked on the host; they select VALUES (sel4), never addresses of the record.
+// Nothing is read or written for p >= P, and a pass writes no stream its map does not name.
+// ---------------------------------------------------------------------------------------------------------
+// one thread per point: point_cell<4>() as the gather calls it, so the record describes exactly the cell whose corners the
+// gather read.  coef[p][24] = {om[0][k], om[1][k], dom[0][k], dom[1][k], kap[k]} at 0 / 4 / 8 / 12 / 16 + k, entries 20 .. 23 = 0.
+__global__ __launch_bounds__(256) void k_coef_nd4(GatherArgs a) {
+  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= (size_t)a.d.P) return;
+  GeomJet gj;
+  point_cell<4>(a.d, a.pts, p, gj);
+  float* cf = a.coef + p * 24;
+  st4(cf, f32x4{gj.om[0][0], gj.om[0][1], gj.om[0][2], gj.om[0][3]});
+  st4(cf + 4, f32x4{gj.om[1][0], gj.om[1][1], gj.om[1][2], gj.om[1][3]});
+  st4(cf + 8, f32x4{gj.dom[0][0], gj.dom[0][1], gj.dom[0][2], gj.dom[0][3]});
+  st4(cf + 12, f32x4{gj.dom[1][0], gj.dom[1][1], gj.dom[1][2], gj.dom[1][3]});
+  st4(cf + 16, f32x4{gj.kap[0], gj.kap[1], gj.kap[2], gj.kap[3]});
+  st4(cf + 20, f32x4{0.f, 0.f, 0.f, 0.f});
+}
+
+extern "C" int stpde_lig_coef_nd4(const stpde_gather_nd_desc* d, const float* pts, float* coef, void* stream) {
+  if (!d || !pts || !coef) {
+    stpde_set_error("lig_coef_nd4: null pointer");
+    return STPDE_E_BADARG;
+  }
+  if (d->D != 4) {
+    stpde_set_error("lig_coef_nd4: D = %d (the record of all four axes: 4; D = 1, 2 have stpde_lig_coef_nd)", d->D);
+    return STPDE_E_BADARG;
+  }
+  const int rc = check_gather_nd_desc("lig_coef_nd4", d);
+  if (rc) return rc;
+  GatherArgs a{};
+  a.d = *d, a.pts = pts, a.coef = coef;
+  STPDE_LAUNCH(k_coef_nd4, dim3((unsigned)(((size_t)a.d.P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return stpde_check_launch("k_coef_nd4");
+}
+
+__device__ __forceinline__ float sel4(int d, float a0, float a1, float a2, float a3) {
+  return d == 0 ? a0 : (d == 1 ? a1 : (d == 2 ? a2 : a3));
+}
+
+struct ReduceNd4Args {
+  stpde_nd4_pass_desc d;
+  int slot0[6], slot1[6];   // pair k in slots of the triple: axis[slot0[k]] = pair0[k] (derived on the host)
+  int P, n_out;
+  long ldp;
+  const float* src;    // out_pre [ntiles][S_mlp][1][256]
+  const float* coef;   // [P][24]
+  float* dst;          // jets [S][n_out][ldp]
+};
+
+// one thread per (point, channel): the 16 corner terms in corner order with the arithmetic of k_reduce_nd_jet.  Slot i of the
+// pass is axis d.axis[i]: f[1 + i] is the tangent stream of that axis, pair k names two slots.
+__global__ __launch_bounds__(256) void k_reduce_nd4_jet(ReduceNd4Args a) {
+  const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (size_t)a.P * a.n_out) return;
+  const size_t p = gid / a.n_out;
+  const int ch = gid % a.n_out;
+  const int S2 = a.d.npairs, S_mlp = a.d.S_mlp;
+  float cf[24];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    f32x4 v = ld4(a.coef + p * 24 + 4 * i);
+    cf[4 * i] = v[0];
+    cf[4 * i + 1] = v[1];
+    cf[4 * i + 2] = v[2];
+    cf[4 * i + 3] = v[3];
+  }
+  float ks[3];   // kappa of the pass's three slots
+#pragma unroll
+  for (int i = 0; i < 3; ++i) ks[i] = sel4(a.d.axis[i], cf[16], cf[17], cf[18], cf[19]);
+  float y[10];
+#pragma unroll
+  for (int s = 0; s < 10; ++s) y[s] = 0.f;
+  for (int corner = 0; corner < 16; ++corner) {
+    const int lane = ((ch >> 2) << 4) | corner;
+    const float* base = a.src + p * (size_t)S_mlp * 256 + lane * 4 + (ch & 3);
+    float f[10];
+#pragma unroll
+    for (int s = 0; s < 10; ++s) f[s] = s < S_mlp ? base[(size_t)s * 256] : 0.f;
+    float om[4], dm[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int bit = corner_bit(corner, 4, k);
+      om[k] = bit ? cf[4 + k] : cf[k];
+      dm[k] = bit ? cf[12 + k] : cf[8 + k];
+    }
+    const float w = om[0] * om[1] * om[2] * om[3];
+    float dw[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int ax = a.d.axis[i];
+      dw[i] = (ax == 0 ? dm[0] : om[0]) * (ax == 1 ? dm[1] : om[1]) * (ax == 2 ? dm[2] : om[2]) * (ax == 3 ? dm[3] : om[3]);
+    }
+    y[0] += w * f[0];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) y[1 + i] += dw[i] * f[0] + w * ks[i] * f[1 + i];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      if (k < S2) {
+        const int d = a.slot0[k], e = a.slot1[k];       // slots < 3 (derived on the host from the pair's axes)
+        const int ad = a.d.pair0[k], ae = a.d.pair1[k];
+        const float kd = sel3(d, ks[0], ks[1], ks[2]), ke = sel3(e, ks[0], ks[1], ks[2]);
+        const float dwd = sel3(d, dw[0], dw[1], dw[2]), dwe = sel3(e, dw[0], dw[1], dw[2]);
+        const float fd = sel3(d, f[1], f[2], f[3]), fe = sel3(e, f[1], f[2], f[3]);
+        float ddw = 0.f;
+        if (d != e)
+          ddw = ((ad == 0 || ae == 0) ? dm[0] : om[0]) * ((ad == 1 || ae == 1) ? dm[1] : om[1]) *
+                ((ad == 2 || ae == 2) ? dm[2] : om[2]) * ((ad == 3 || ae == 3) ? dm[3] : om[3]);
+        y[4 + k] += ddw * f[0] + dwd * ke * fe + dwe * kd * fd + w * kd * ke * f[4 + k];
+      }
+    }
+  }
+  if (a.d.dst_value >= 0) a.dst[((size_t)a.d.dst_value * a.n_out + ch) * a.ldp + p] = y[0];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    if (a.d.dst_first[i] >= 0) a.dst[((size_t)a.d.dst_first[i] * a.n_out + ch) * a.ldp + p] = y[1 + i];
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+    if (k < S2 && a.d.dst_pair[k] >= 0) a.dst[((size_t)a.d.dst_pair[k] * a.n_out + ch) * a.ldp + p] = y[4 + k];
+}
+
+extern "C" int stpde_lig_reduce_nd4_jet_fwd(const stpde_nd4_pass_desc* d, int D, int P, int ntiles, int n_out, const float* out_pre,
+                                            const float* coef, float* jets, long ldp, void* stream) {
+  const char* who = "lig_reduce_nd4_jet_fwd";
+  if (!d || !out_pre || !coef || !jets) {
+    stpde_set_error("%s: null pointer", who);
+    return STPDE_E_BADARG;
+  }
+  if (D != 4) {
+    stpde_set_error("%s: D = %d (passes over axis triples of a 4-d grid: 4; D = 1, 2 have stpde_lig_reduce_nd_jet_fwd)", who, D);
+    return STPDE_E_BADARG;
+  }
+  const int rc = check_nd(who, 4, P, ntiles);
+  if (rc) return rc;
+  if (n_out < 1 || n_out > 16 || ldp < P) {
+    stpde_set_error("%s: n_out = %d (1..16) or ldp < P", who, n_out);
+    return STPDE_E_BADARG;
+  }
+  if (d->axis[0] < 0 || d->axis[0] >= d->axis[1] || d->axis[1] >= d->axis[2] || d->axis[2] >= 4) {
+    stpde_set_error("%s: axis triple (%d, %d, %d) is not strictly increasing inside 0..3", who, d->axis[0], d->axis[1], d->axis[2]);
+    return STPDE_E_BADARG;
+  }
+  if (d->npairs != 0 && d->npairs != 2 && d->npairs != 4 && d->npairs != 6) {
+    stpde_set_error("%s: npairs = %d (the S2 of a stream set: 0, 2, 4 or 6)", who, d->npairs);
+    return STPDE_E_BADARG;
+  }
+  if (d->S_mlp != 4 && d->S_mlp != 4 + d->npairs) {
+    stpde_set_error("%s: S_mlp = %d (4, or 4 + npairs = %d)", who, d->S_mlp, 4 + d->npairs);
+    return STPDE_E_BADARG;
+  }
+  if (d->S < 1 || d->S > 15) {
+    stpde_set_error("%s: S = %d streams of the jets tensor (1..15)", who, d->S);
+    return STPDE_E_BADARG;
+  }
+  ReduceNd4Args a{};
+  a.d = *d;
+  for (int k = 0; k < d->npairs; ++k) {
+    int s0 = -1, s1 = -1;
+    for (int i = 0; i < 3; ++i) {
+      if (d->axis[i] == d->pair0[k]) s0 = i;
+      if (d->axis[i] == d->pair1[k]) s1 = i;
+    }
+    if (s0 < 0 || s1 < 0) {
+      stpde_set_error("%s: pair %d = (%d, %d) names an axis outside the triple (%d, %d, %d)", who, k, d->pair0[k], d->pair1[k],
+                      d->axis[0], d->axis[1], d->axis[2]);
+      return STPDE_E_BADARG;
+    }
+    a.slot0[k] = s0, a.slot1[k] = s1;
+  }
+  int dsts[10], nd = 0;
+  dsts[nd++] = d->dst_value;
+  for (int i = 0; i < 3; ++i) dsts[nd++] = d->dst_first[i];
+  for (int k = 0; k < d->npairs; ++k) dsts[nd++] = d->dst_pair[k];
+  for (int i = 0; i < nd; ++i) {
+    if (dsts[i] < -1 || dsts[i] >= d->S) {
+      stpde_set_error("%s: destination stream %d outside [-1, %d)", who, dsts[i], d->S);
+      return STPDE_E_BADARG;
+    }
+    for (int j = 0; j < i; ++j)
+      if (dsts[i] >= 0 && dsts[i] == dsts[j]) {
+        stpde_set_error("%s: destination stream %d named twice", who, dsts[i]);
+        return STPDE_E_BADARG;
+      }
+  }
+  a.P = P, a.n_out = n_out, a.ldp = ldp, a.src = out_pre, a.coef = coef, a.dst = jets;
+  const size_t n = (size_t)P * n_out;
+  STPDE_LAUNCH(k_reduce_nd4_jet, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return stpde_check_launch("k_reduce_nd4_jet");
 }
 
 // ---------------------------------------------------------------------------------------------------------

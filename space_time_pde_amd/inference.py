@@ -44,7 +44,7 @@ def evaluate_lattice(pde_layer, latent_grid, seqs, channels, pseudo_batch_size=1
 
     Returns {name in ``channels`` (the outputs, in order) or equation name: ndarray [len(seqs[0]), ..., len(seqs[d - 1])]} for
     batch element 0.  Grad mode as in ``evaluate_feat_grid``: off where the layer answers with forward-mode jets (for 1- and
-    2-d problems that is the opt-in ``lig_jet.nd_jets``; whether it does is asked with grad mode off, the mode those jets
+    2-d problems that is the opt-in ``lig_jet.nd_jets``, for 4-d ones ``lig_jet.nd4_jets``; whether it does is asked with grad mode off, the mode those jets
     need), on for the reverse sweeps of the generic strategy.
     """
     device = latent_grid.device

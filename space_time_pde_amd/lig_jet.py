@@ -1,5 +1,6 @@
 """Host driver of the fused LIG + IM-NET jet path (dim = 3; value queries, and opt-in their training backward, also for
-dim = 1, 2, 4; opt-in jets, and opt-in their training backward, also for dim = 1, 2) on libstpde_hip.
+dim = 1, 2, 4; opt-in jets, and opt-in their training backward, also for dim = 1, 2; opt-in jets of forward passes also for
+dim = 4, as passes over axis triples) on libstpde_hip.
 
 Computes y = query_local_implicit_grid(imnet, latent, pts) together with its first and selected second
 derivatives w.r.t. the query coordinates ("jets") in one forward pass of HIP kernels, and the gradients w.r.t.
@@ -21,7 +22,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import XT, GatherDesc, GatherNdDesc, ImNetPlanDesc, JetCfg, LayerDesc, LigWorkspace, XbarDesc, check, ptr, stream_ptr
+from ._lib import (XT, GatherDesc, GatherNdDesc, ImNetPlanDesc, JetCfg, LayerDesc, LigWorkspace, Nd4PassDesc, XbarDesc, check, ptr,
+                   stream_ptr)
 
 _FRAG = 256  # floats per 16x16 fragment block
 # widest latent the HIP jet path takes: the augmented input [r(3); latent(c); 1] must fit XT = 3 fragment tiles whose third
@@ -72,6 +74,20 @@ def set_nd_jet_backward(on):
     the previous setting."""
     global nd_jet_backward
     prev, nd_jet_backward = nd_jet_backward, bool(on)
+    return prev
+
+
+# Opt-in: coordinate derivatives of queries on 4-d grids -- 3-d space + time -- in HIP, for forward passes that need no gradient
+# (``set_nd4_jets`` / STPDE_ND4_JETS=1, read once here; independent of ``nd_jets``, and ``ND_JET_DIMS`` stays what it is).  The
+# layer kernels carry three first-order streams, so such a request runs as up to four PASSES over axis triples (``nd4_passes``).
+# Off, lig_jets refuses a derivative request on a 4-d grid and PDELayer runs its reverse sweeps through the composed formulation.
+nd4_jets = os.getenv("STPDE_ND4_JETS", "0").strip().lower() not in ("", "0", "false", "no", "off")
+
+
+def set_nd4_jets(on):
+    """Switch the HIP coordinate derivatives of dim = 4 queries on or off; returns the previous setting."""
+    global nd4_jets
+    prev, nd4_jets = nd4_jets, bool(on)
     return prev
 
 
@@ -151,6 +167,44 @@ class ImNetPlan:
         self.n_theta = theta_off
         self._build_indices()
         self._dev = {}
+        # dim = 4 (``nd4_jets``): {axis triple: [per layer] index array [3][MT][64][4]} of the `tanc` packs of the passes over
+        # the triples other than (0, 1, 2) -- BESIDE pack_index_np, built when a derivative request first needs one (tanc_index)
+        self.tanc_nd4 = {}
+
+    def tanc_index(self, triple):
+        """dim = 4: the index arrays of the tangent constants of a pass over the axis triple (a0 < a1 < a2), one per layer in the
+        layout of the "tanc" pack, [3][MT][64][4]: block (k, mt), lane (g, j), register r = W_s,l[16 mt + 4 g + r, coordinate
+        a_k] -- column a_k of the skip block (feature a sits in slot a) -- and the plan's zero for rows past M and for fc5, which
+        has no skip block.  (0, 1, 2) is what the "tanc" pack itself holds.  Nothing of pack_index_np / pack_off moves."""
+        triple = tuple(int(a) for a in triple)
+        if self.dim != 4 or len(triple) != 3 or not (0 <= triple[0] < triple[1] < triple[2] < 4):
+            raise ValueError("tanc_index: a strictly increasing axis triple of a dim = 4 plan, not %r" % (triple,))
+        if triple not in self.tanc_nd4:
+            zero = self.n_theta
+            g = np.arange(64) >> 4
+            out = []
+            for lay in self.layers:
+                row = 16 * np.arange(lay["MT"])[:, None, None] + 4 * g[None, :, None] + np.arange(4)[None, None, :]
+                col = lay["w_off"] + row * lay["Kin"] + lay["Kh"]
+                live = (row < lay["M"]) & bool(lay["skip"])
+                out.append(np.stack([np.where(live, col + a, zero) for a in triple], 0).astype(np.int64))
+            self.tanc_nd4[triple] = out
+        return self.tanc_nd4[triple]
+
+    def pack_tanc(self, params, triples):
+        """the `tanc` packs of the passes over ``triples``: {triple: [per layer] flat fp32 tensors}; the parameters are
+        concatenated once, every pack is one index gather from them.  No triple: nothing is done."""
+        if not triples:
+            return {}
+        dev = params[0].device
+        theta = torch.cat([p.detach().reshape(-1).float() for p in params] + [torch.zeros(1, device=dev)])
+        out = {}
+        for triple in triples:
+            key = (str(dev), tuple(triple))
+            if key not in self._dev:
+                self._dev[key] = [torch.from_numpy(ix.reshape(-1)).to(dev) for ix in self.tanc_index(triple)]
+            out[tuple(triple)] = [theta[ix] for ix in self._dev[key]]
+        return out
 
     def _build_indices(self):
         zero = self.n_theta  # index of the appended 0.0
@@ -320,6 +374,56 @@ def make_cfg(act, act_param, first, pairs, combo=None):
     return cfg, 1 + s1 + s2, pp
 
 
+# ------------------------------------------------------------------------------------------------------------
+# dim = 4: the pass schedule.  The layer kernels carry three first-order streams; a mixed second derivative needs the streams of
+# its two axes only, and the four axis triples of {0, 1, 2, 3} hold all six mixed pairs: any request is at most four passes.
+# ------------------------------------------------------------------------------------------------------------
+ND4_TRIPLES = ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3))
+
+
+def _nd4_s2(n):
+    """pairs of a pass padded to the S2 of a compiled stream set, as make_cfg pads them"""
+    if n <= 2:
+        return 2 * (n > 0)
+    return 4 if (n <= 4 and os.environ.get("STPDE_S34", "1") != "0") else 6
+
+
+def nd4_passes(first, pairs):
+    """The passes of a derivative request on a 4-d grid: [(triple, pairs of the pass, dst_map)], a pure function of the request.
+
+    pairs: distinct second-derivative pairs (a, b), axes < 4, in the caller's order; the caller's jets tensor is
+    [1 + 4 + len(pairs)]: value, d/dq_0 .. d/dq_3, then the pairs.  ``first`` -- or any pair, as in make_cfg -- asks for all four
+    first-order streams.  triple: the strictly increasing axes whose tangent streams the pass carries.  pairs of the pass: in
+    axes, padded to an even count (2, 4, 6) by repeating the last one.  dst_map = (value, (f0, f1, f2), (p0, ...)): the stream of
+    the jets tensor that receives the value, the derivative along triple[k] and each pair of the pass, or -1 (not stored).
+    Every pair belongs to exactly one pass whose triple holds both its axes -- the first such pass --, every first-order axis
+    is stored by the first pass that carries it, the value by pass 0 alone.  The passes are the first subset of ND4_TRIPLES,
+    enumerated by size and then in lexicographic order, whose triples hold every requested pair and axis: their number is the
+    minimum.  A triple holds six pairs at most, so no pass carries more.  A request for the value alone is one pass that stores
+    nothing else (lig_jets serves it on the value path instead)."""
+    import itertools
+    pairs = [tuple(sorted((int(a), int(b)))) for a, b in pairs]
+    if any(not (0 <= a <= b < 4) for a, b in pairs):
+        raise ValueError("dim = 4: second-derivative pairs %r name an axis the grid does not have" % (pairs,))
+    if len(set(pairs)) != len(pairs):
+        raise ValueError("dim = 4: second-derivative pairs %r name a pair twice" % (pairs,))
+    axes = set(range(4)) if (first or pairs) else set()
+    for size in range(1, 5):
+        for sub in itertools.combinations(ND4_TRIPLES, size):
+            if axes <= set().union(*sub) and all(any(set(pr) <= set(t) for t in sub) for pr in pairs):
+                out, stored = [], set()
+                for k, t in enumerate(sub):
+                    own = [(pr, 5 + i) for i, pr in enumerate(pairs)
+                           if set(pr) <= set(t) and not any(set(pr) <= set(u) for u in sub[:k])]
+                    fdst = tuple(1 + a if (a in axes and a not in stored) else -1 for a in t)
+                    stored |= set(t)
+                    pad = _nd4_s2(len(own)) - len(own)
+                    out.append((t, [pr for pr, _ in own] + ([own[-1][0]] * pad if pad else []),
+                                (0 if k == 0 else -1, fdst, tuple(s for _, s in own) + (-1,) * pad)))
+                return out
+    raise AssertionError("unreachable: the four triples hold every pair and every axis")
+
+
 def box_constants(shape3, xmin, xmax):
     """lo_c, hi_c, cube with the reference's own fp32 expression sequence
     (src/regular_nd_grid_interpolation.py:40-51), evaluated on the host."""
@@ -399,6 +503,33 @@ def _tail_applies(fused_tail, nf, cfg, combo, value_tiles=False):
 
 
 @dataclasses.dataclass(frozen=True, eq=False)
+class Nd4Pass:
+    """One pass of a derivative request on a 4-d grid (``nd4_passes``) as the driver runs it."""
+    triple: tuple           # the axes whose tangent streams the layer kernels carry: slot k of the pass = axis triple[k]
+    cfg: JetCfg             # the pass's stream set; its pairs name SLOTS of the triple
+    S: int                  # streams of the layer buffers in this pass
+    desc: Nd4PassDesc       # what stpde_lig_reduce_nd4_jet_fwd takes: axes, pairs in axes, the destination-stream map
+
+
+def _nd4_records(act, act_param, first, pairs, S_out):
+    """nd4_passes as Nd4Pass records.  A piecewise-linear activation carries value + tangents only, (3, 0): the reduction
+    supplies the second derivatives from the weight cross terms, as for every other dimension."""
+    linear = act in ("relu", "leakyrelu")
+    recs = []
+    for triple, pp, (dst_value, dst_first, dst_pair) in nd4_passes(first, pairs):
+        cfg, S, padded = make_cfg(act, act_param, True, [] if linear else [(triple.index(a), triple.index(b)) for a, b in pp])
+        assert linear or len(padded) == len(pp)
+        d = Nd4PassDesc()
+        d.npairs, d.S_mlp, d.S, d.dst_value = len(pp), S, S_out, dst_value
+        for k in range(3):
+            d.axis[k], d.dst_first[k] = triple[k], dst_first[k]
+        for k, (a, b) in enumerate(pp):
+            d.pair0[k], d.pair1[k], d.dst_pair[k] = a, b, dst_pair[k]
+        recs.append(Nd4Pass(triple, cfg, S, d))
+    return tuple(recs)
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
 class JetCall:
     """What one jet call is and how it runs, decided ONCE when the call is made (``JetCall.make``) and read by every later
     stage: the forward, its chunks, the backward and a stash rebuild inside the backward.  Frozen -- except ``chunk``."""
@@ -447,6 +578,10 @@ class JetCall:
     SP0: int                # streams of the layer-0 adjoint: value (+ 3 tangents)
     split0: bool            # ... kept as value blocks + tangent row sums
     mult: int               # points a launch chunk is a multiple of
+    # ---- dim = 4 derivative requests (``nd4_jets``); cfg / S above are then those of the WIDEST pass: the layer buffers are
+    #      sized for it and reused from pass to pass
+    nd4_jets: bool = False  # dim = 4: coordinate derivatives in HIP are allowed (forward passes that need no gradient)
+    passes: tuple = ()      # the Nd4Pass records of the request; empty for every other call
 
     @classmethod
     def make(cls, plan, act, act_param, first, pairs, combo, precision, grid_shape, box, budget=None, B=1, N=0,
@@ -463,10 +598,24 @@ class JetCall:
         # output streams (what the caller gets) vs MLP streams (what the layer kernels carry): for piecewise-linear
         # activations sigma'' = 0 makes every second-order MLP stream identically zero, so only value + gradient streams
         # go through the network and the reduction supplies the second derivatives from the weight cross terms
-        cfg_out, S_out, ppairs = make_cfg(act, act_param, first, list(pairs), combo)
-        cfg, S = cfg_out, S_out
-        if act in ("relu", "leakyrelu") and ppairs:
-            cfg, S, _ = make_cfg(act, act_param, True, [])
+        passes = ()
+        if dim == 4 and (first or len(pairs) or combo):
+            # 3-d space + time: the request runs as passes over axis triples.  cfg_out stands for "value + tangents, no combined
+            # stream" (nothing reads its pairs), the caller's streams are value, four first-order ones and the pairs as asked
+            if not nd4_jets:
+                raise NotImplementedError(_ND_VALUE_ONLY % dim)
+            if combo:
+                raise NotImplementedError("dim = 4: the combined second-order stream is dim = 3 only (ask for the pairs)")
+            ppairs = [tuple(sorted((int(a), int(b)))) for a, b in pairs]
+            S_out = 1 + 4 + len(ppairs)
+            passes = _nd4_records(act, act_param, first, ppairs, S_out)
+            cfg_out = make_cfg(act, act_param, True, [])[0]
+            cfg, S = max(((ps.cfg, ps.S) for ps in passes), key=lambda cs: cs[1])
+        else:
+            cfg_out, S_out, ppairs = make_cfg(act, act_param, first, list(pairs), combo)
+            cfg, S = cfg_out, S_out
+            if act in ("relu", "leakyrelu") and ppairs:
+                cfg, S, _ = make_cfg(act, act_param, True, [])
         tail = _tail_applies(fused_tail, plan.nf, cfg, cfg_out.combo)
         # bf16 mode, reference width: the stashes of the hidden layers' output rows and their adjoints in the PACKED form -- all
         # of their consumers are bf16-operand kernels (layers 1-2: k_layer_coop / k_wgrad_coop; fc3 -> fc5: k_tail_fwd_bf /
@@ -493,7 +642,8 @@ class JetCall:
                    nd_backward=bool(nd_backward), nd_jets=bool(nd_jets),
                    nd_jet_backward=bool(nd_jets and nd_jet_backward),
                    pipeline=bool(use_pipeline and profile is None and dim == 3),
-                   tail=tail, SP0=SP0, split0=bool(SP0 == 4 and tan0_rowsum), mult=mult)
+                   tail=tail, SP0=SP0, split0=bool(SP0 == 4 and tan0_rowsum), mult=mult,
+                   nd4_jets=bool(nd4_jets), passes=passes)
 
     def plan_chunk(self, points):
         """the one write of the record: ``chunk``, by the memory plan (LigJetFunction.forward; lig_jets: the n-D default)"""
@@ -610,7 +760,7 @@ def nd_tiles(P, dim):
 # ------------------------------------------------------------------------------------------------------------
 _LAYER_BUFS = tuple("buf%d" % l for l in range(1, 6))
 _FWD_ORDER = {True: ("X", "cw", "coef", "cell") + _LAYER_BUFS + ("z0",),
-              False: ("X", "cw", "roww", "coef", "cell", "buf1", "z0") + _LAYER_BUFS[1:]}
+              False: ("X", "cw", "roww", "coef", "coef4", "cell", "buf1", "z0") + _LAYER_BUFS[1:]}
 _BWD_ORDER = {True: ("abar2x", "abar3x", "abar1x", "abar4x", "abar0x", "tan0", "abar0"),
               False: ("abar0", "abar0x", "tan0", "abar1x", "abar4x", "abar3x", "abar2x")}
 _DTYPES = dict(cell=torch.int32, perm=torch.int32, start=torch.int32, sort_tmp=torch.uint8)     # every other one: fp32
@@ -631,11 +781,13 @@ def _chunk_tiles(call, Pc):
 def _forward_buffers(call, Pc, need_grad=True):
     """Forward chunk: the fragment image X of the augmented input, what the gather records per point (dim = 3: row weights of
     a combined second-order stream, interpolation coefficients, cell index; dim = 1, 2, 4: the corner weight of every row, and
-    coefficients for a derivative request only), the five layer buffers, and -- a backward can follow -- the value stream z0
-    of the layer-0 pre-activations."""
+    coefficients for a derivative request only -- dim = 4: the wider record of all four axes, ``coef4``), the five layer buffers
+    (dim = 4: of the widest pass, ``call.S`` streams), and -- a backward can follow -- the value stream z0 of the layer-0
+    pre-activations."""
     nd, nt = call.plan.dim != 3, _chunk_tiles(call, Pc)
     size = dict(X=nt * XT * _FRAG, cw=Pc * 8 if call.cfg_out.combo else None, roww=nt * 16 if nd else None,
-                coef=Pc * 16 if (not nd or call.S_out > 1) else None, cell=None if nd else Pc,
+                coef=Pc * 16 if ((not nd or call.S_out > 1) and not call.passes) else None,
+                coef4=Pc * 24 if call.passes else None, cell=None if nd else Pc,
                 z0=nt * call.plan.layers[0]["MT"] * _FRAG if need_grad else None)
     size.update(("buf%d" % l, _buf_floats(call, l, nt)) for l in range(1, 6))
     return _table(_FWD_ORDER[call.pipeline], size)
@@ -741,10 +893,15 @@ def _gather_nd_desc(call, latent, Pc, p0, nt):
     return gd
 
 
-def _forward_chunk(call, packs, packs16, latent, pts_c, jets, p0, need_grad=True):
-    """Run gather + layers 1..5 + reduce for points [p0, p0+Pc) ; returns the buffers backward needs."""
+def _forward_chunk(call, packs, packs16, latent, pts_c, jets, p0, need_grad=True, tancs=None):
+    """Run gather + layers 1..5 + reduce for points [p0, p0+Pc) ; returns the buffers backward needs.
+
+    dim = 4 with derivative streams (``call.passes``): the gather and stpde_lig_coef_nd4 once, then per pass layers 1..5 with
+    the pass's stream set and `tanc` packs (``tancs`` = {triple: [per layer]}, ImNetPlan.pack_tanc; (0, 1, 2) is the plan's own
+    pack) into the SAME layer buffers, and stpde_lig_reduce_nd4_jet_fwd into the streams of ``jets`` the pass owns."""
     nd = call.plan.dim != 3       # query on a 1-, 2- or 4-d grid: own gather / corner sum, the same layer kernels
-    nd_jet = nd and call.S_out > 1    # ... with derivative streams (dim = 1, 2, ``nd_jets``; lig_jets let nothing else through)
+    nd4 = bool(call.passes)       # ... with derivative streams on a 4-d grid (``nd4_jets``)
+    nd_jet = nd and call.S_out > 1 and not nd4    # ... on a 1- / 2-d grid (``nd_jets``; lig_jets let nothing else through)
     if call.pipeline:
         return _forward_chunk_c(call, packs, packs16, latent, pts_c, jets, p0, need_grad)
     plan, cfg, S = call.plan, call.cfg, call.S
@@ -760,6 +917,9 @@ def _forward_chunk(call, packs, packs16, latent, pts_c, jets, p0, need_grad=True
         gd = _gather_nd_desc(call, latent, Pc, p0, nt)
         with _timed("gather_nd"):
             check(L.stpde_lig_gather_nd(C.byref(gd), ptr(pts_c), ptr(latent), ptr(X), ptr(roww), st))
+        if nd4:
+            with _timed("coef_nd4"):
+                check(L.stpde_lig_coef_nd4(C.byref(gd), ptr(pts_c), ptr(s["coef4"]), st))
         if nd_jet:
             with _timed("coef_nd"):
                 check(L.stpde_lig_coef_nd(C.byref(gd), ptr(pts_c), ptr(coef), st))
@@ -776,28 +936,42 @@ def _forward_chunk(call, packs, packs16, latent, pts_c, jets, p0, need_grad=True
         lcfg = JetCfg()
         lcfg.S1, lcfg.S2, lcfg.act, lcfg.act_param = 0, 3, cfg.act, cfg.act_param
         lnt = nt // 4
-    # fc3 -> fc4 -> fc5 in one kernel (inter-layer data in registers) for the reference widths and the training stream sets
-    tail = _tail_applies(call.fused_tail, plan.nf, cfg, call.cfg_out.combo, vt)
-    for l in range(1, 6):
-        lay = plan.layers[l]
-        if tail and l == 3:
-            arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
-            pk_tail = (call.packed_mask >> 2) & 1         # bf16 mode: packed buffers on both sides, bf16-operand kernel
-            w16s = arr([packs16[(k, "Wh")] for k in (3, 4, 5)]) if pk_tail else None
-            with _timed("tail_fwd"):
-                check(L.stpde_jet_tail_fwd_p(C.byref(lcfg), lnt, plan.nf // 16, ptr(bufs[2]), ptr(X),
-                                             arr([pv(packs, k, "Wh") for k in (3, 4, 5)]),
-                                             arr([pv(packs, k, "Ws") for k in (3, 4, 5)]),
-                                             arr([pv(packs, k, "tanc") for k in (3, 4, 5)]), arr(bufs[3:6]), ptr(cw),
-                                             3 if pk_tail else 0, w16s, st))
-            break
-        w16 = packs16.get((l, "Wh")) if packs16 else None
-        d = _layer_desc(call, lnt, lay, lcfg, l == 1, call.nsplit if w16 is not None else 0, _pk(call, l, l) & 3)
-        with _timed("layer%d_fwd" % l):
-            check(L.stpde_jet_layer_fwd(C.byref(d), ptr(bufs[l - 1]), ptr(X), ptr(pv(packs, l, "Wh")),
-                                        ptr(pv(packs, l, "Ws")), ptr(pv(packs, l, "tanc")), ptr(pv(packs, 0, "Ws")),
-                                        ptr(pv(packs, 0, "tanc")), ptr(bufs[l]), ptr(cw), ptr(w16),
-                                        ptr(z0) if l == 1 else None, st))
+    def layers(lcfg, lnt, tail_cfg, tc):
+        """layers 1 .. 5 over ``lnt`` tiles in the stream set ``lcfg``; tail_cfg: the stream set that decides whether the fused
+        fc3 -> fc5 kernel serves them (a value-tile pass runs in its own ``lcfg`` and is decided by the call's);
+        tc(l): the tangent constants of layer l"""
+        # fc3 -> fc4 -> fc5 in one kernel (inter-layer data in registers) for the reference widths and the training stream sets
+        tail = _tail_applies(call.fused_tail, plan.nf, tail_cfg, call.cfg_out.combo, vt)
+        for l in range(1, 6):
+            lay = plan.layers[l]
+            if tail and l == 3:
+                arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
+                pk_tail = (call.packed_mask >> 2) & 1         # bf16 mode: packed buffers on both sides, bf16-operand kernel
+                w16s = arr([packs16[(k, "Wh")] for k in (3, 4, 5)]) if pk_tail else None
+                with _timed("tail_fwd"):
+                    check(L.stpde_jet_tail_fwd_p(C.byref(lcfg), lnt, plan.nf // 16, ptr(bufs[2]), ptr(X),
+                                                 arr([pv(packs, k, "Wh") for k in (3, 4, 5)]),
+                                                 arr([pv(packs, k, "Ws") for k in (3, 4, 5)]),
+                                                 arr([tc(k) for k in (3, 4, 5)]), arr(bufs[3:6]), ptr(cw),
+                                                 3 if pk_tail else 0, w16s, st))
+                break
+            w16 = packs16.get((l, "Wh")) if packs16 else None
+            d = _layer_desc(call, lnt, lay, lcfg, l == 1, call.nsplit if w16 is not None else 0, _pk(call, l, l) & 3)
+            with _timed("layer%d_fwd" % l):
+                check(L.stpde_jet_layer_fwd(C.byref(d), ptr(bufs[l - 1]), ptr(X), ptr(pv(packs, l, "Wh")),
+                                            ptr(pv(packs, l, "Ws")), ptr(tc(l)), ptr(pv(packs, 0, "Ws")),
+                                            ptr(tc(0)), ptr(bufs[l]), ptr(cw), ptr(w16),
+                                            ptr(z0) if l == 1 else None, st))
+
+    if nd4:
+        for ps in call.passes:
+            own = None if ps.triple == ND4_TRIPLES[0] else tancs[ps.triple]
+            layers(ps.cfg, nt, ps.cfg, (lambda l: pv(packs, l, "tanc")) if own is None else (lambda l: own[l]))
+            with _timed("reduce_nd4_jet"):
+                check(L.stpde_lig_reduce_nd4_jet_fwd(C.byref(ps.desc), plan.dim, Pc, nt, plan.cout, ptr(bufs[5]), ptr(s["coef4"]),
+                                                     C.c_void_p(jets.data_ptr() + 4 * p0), jets.shape[2], st))
+        return None     # (forward only: no stash)
+    layers(lcfg, lnt, cfg, lambda l: pv(packs, l, "tanc"))
     if nd_jet:
         with _timed("reduce_nd_jet"):
             check(L.stpde_lig_reduce_nd_jet_fwd(C.byref(call.cfg_out), S, plan.dim, Pc, nt, plan.cout, ptr(bufs[5]), ptr(coef),
@@ -1090,6 +1264,8 @@ class LigJetFunction(torch.autograd.Function):
         # act_param: the learnable swish beta (a tensor input so that autograd routes its gradient) or None
         packs = call.plan.pack(params)
         packs16 = call.plan.pack_bf16(packs, call.nsplit) if call.bf16 else None
+        # dim = 4 derivative request: the tangent constants of the passes over the triples other than (0, 1, 2)
+        tancs = call.plan.pack_tanc(params, [ps.triple for ps in call.passes if ps.triple != ND4_TRIPLES[0]])
         P = pts.shape[0]
         jets = torch.empty(call.S_out, call.plan.cout, P, device=pts.device)
         # grad mode is always off inside Function.forward and ctx.needs_input_grad ignores torch.no_grad(): whether a
@@ -1117,7 +1293,7 @@ class LigJetFunction(torch.autograd.Function):
         oom = False
         try:
             for p0, n in _chunk_ranges(call, P):
-                s = _forward_chunk(call, packs, packs16, latent, pts[p0:p0 + n], jets, p0, need_grad and not recompute)
+                s = _forward_chunk(call, packs, packs16, latent, pts[p0:p0 + n], jets, p0, need_grad and not recompute, tancs)
                 if need_grad and not recompute:
                     saved.append(s)
         except torch.OutOfMemoryError:
@@ -1135,7 +1311,7 @@ class LigJetFunction(torch.autograd.Function):
             recompute = True
             call.plan_chunk(min(call.chunk, _recompute_chunk(call, pts.device)))
             for p0, n in _chunk_ranges(call, P):
-                _forward_chunk(call, packs, packs16, latent, pts[p0:p0 + n], jets, p0, False)
+                _forward_chunk(call, packs, packs16, latent, pts[p0:p0 + n], jets, p0, False, tancs)
         stats["recompute_steps"] += int(recompute)
         ctx.recompute = recompute
         ctx.call, ctx.packs, ctx.packs16, ctx.saved = call, packs, packs16, saved
@@ -1322,6 +1498,13 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
     dim = 3 stream order; the streams d/dq_k, k >= dim, are +0.0.  Refused: ``combo``, a call that needs a gradient, bf16
     operands, dim = 4.
 
+    imnet.dim = 4 with ``nd4_jets`` (``set_nd4_jets(True)`` / STPDE_ND4_JETS=1; independent of ``nd_jets``): ``first`` /
+    ``pairs`` (distinct, indices < 4, any number of the ten) are served for calls that need no gradient, as up to four passes of
+    the layer kernels over axis triples (``nd4_passes``) between one stpde_lig_gather_nd / stpde_lig_coef_nd4 per chunk and one
+    stpde_lig_reduce_nd4_jet_fwd per pass.  Returns (jets [1 + 4 + len(pairs), n_out, b*p], the pairs as asked): value,
+    d/dq_0 .. d/dq_3, then the pairs in the caller's order, no padding.  Refused: ``combo``, a call that needs a gradient
+    (whatever the other switches say), bf16 operands, in_features > 31.
+
     ... and with ``nd_jet_backward`` on top (``set_nd_jet_backward(True)`` / STPDE_ND_JET_BACKWARD=1; inert without
     ``nd_jets``, independent of ``nd_backward``): such a call may need a gradient -- the jets are differentiable w.r.t. the
     latent grid and the IM-NET parameters (a learnable swish beta included), which is what training with an equation loss on
@@ -1345,7 +1528,7 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
     elif dim in ND_VALUE_DIMS:
         if latent_grid.dim() != dim + 2 or query_pts.dim() != 3 or query_pts.shape[-1] != dim:
             raise ValueError("lig_jets expects latent_grid [b,n_1..n_%d,c] and query_pts [b,p,%d]" % (dim, dim))
-        if wants_jets and dim not in ND_JET_DIMS:
+        if wants_jets and dim not in ND_JET_DIMS and dim != 4:      # (dim = 4: decided with the call's frozen switch, below)
             raise NotImplementedError(_ND_VALUE_ONLY % dim)
         if min(latent_grid.shape[1:-1]) < 2:
             raise ValueError("every axis of the latent grid needs at least 2 nodes")
@@ -1377,15 +1560,16 @@ def lig_jets(imnet, latent_grid, query_pts, xmin, xmax, first=True, pairs=(), ch
     call = JetCall.make(plan, act, prm, first, pairs, combo, precision, grid_shape, cached_box_constants(grid_shape, xmin, xmax),
                         memory_budget, B, N, chunk_points, need_grad)
     if dim != 3 and wants_jets:
-        # dim = 1, 2: whether derivative requests are served is one of the call's frozen switches
-        if not call.nd_jets:
+        # dim = 1, 2 / dim = 4: whether derivative requests are served is one of the call's frozen switches (dim = 4 with
+        # ``nd4_jets`` off was refused by JetCall.make, which cannot lay such a request out)
+        if not (call.nd4_jets if dim == 4 else call.nd_jets):
             raise NotImplementedError(_ND_VALUE_ONLY % dim)
         if combo:
             raise NotImplementedError("dim = %d: the combined second-order stream is dim = 3 only (ask for the pairs)" % dim)
         if any(not (0 <= a < dim and 0 <= b < dim) for a, b in pairs):
             raise ValueError("dim = %d: second-derivative pairs %r name an axis the grid does not have" % (dim, list(pairs)))
         if need_grad:
-            if not call.nd_jet_backward:
+            if dim == 4 or not call.nd_jet_backward:
                 raise NotImplementedError("dim = %d coordinate derivatives run in HIP as forward passes only: call under "
                                           "torch.no_grad() or without inputs / parameters that require grad" % dim)
             # the training backward of the derivative streams runs on one device (and kernel by kernel: ``JetCall.pipeline`` is

@@ -9,7 +9,8 @@ Value-only queries on 1-, 2- and 4-d grids (no jet request, nothing that needs a
 a corner sum of their own around the same IM-NET layer kernels (``_nd_value_eligible``).  With ``lig_jet.nd_backward``
 (opt-in) such a query also trains in HIP: gradients w.r.t. the latent grid and the IM-NET parameters (``_nd_train_eligible``).
 With ``lig_jet.nd_jets`` (opt-in) a PDE layer's derivative request on a 1- or 2-d grid that needs no gradient is answered by
-the HIP jet kernels too (``_nd_jet_eligible``); with ``lig_jet.nd_jet_backward`` on top (opt-in) so is one that trains
+the HIP jet kernels too (``_nd_jet_eligible``), and with ``lig_jet.nd4_jets`` (opt-in, a switch of its own) so is one on a 4-d
+grid -- 3-d space + time --, as passes over axis triples; with ``lig_jet.nd_jet_backward`` on top (opt-in) so is one that trains
 through the residuals: gradients w.r.t. the latent grid and the IM-NET parameters (``_nd_jet_train_eligible``).
 Other decoders / dimensions / requests use the generic composed formulation.
 """
@@ -118,10 +119,17 @@ def _nd_jet_eligible(model, latent_grid, query_pts, req=None):
     ``_nd_value_eligible`` asks for other than its request clause (ImNet decoder, CUDA fp32, nf a multiple of 16, out_features
     <= 16, d + in_features + 1 <= 36, every axis >= 2 nodes, fp32 or fp32x3 operands); and nothing that needs a gradient
     (no_grad, or no point / latent grid / parameter requiring grad; a request that does is ``_nd_jet_train_eligible``'s).
-    d = 4 and point gradients keep the composed formulation."""
-    if not lig_jet.nd_jets or req is None or req.x is not query_pts or req.combo:
+    Point gradients keep the composed formulation.
+
+    d = 4 -- 3-d space + time -- has a switch of its own (opt-in: ``lig_jet.nd4_jets``, ``lig_jet.set_nd4_jets`` /
+    STPDE_ND4_JETS=1; ``nd_jets`` alone leaves such a request composed): the same conditions with d = 4 (in_features <= 31,
+    pair indices < 4, no combined stream, nothing that needs a gradient); the request runs as passes over axis triples
+    (``lig_jet.nd4_passes``)."""
+    if req is None or req.x is not query_pts or req.combo:
         return False
-    if not isinstance(model, ImNet) or model.dim not in lig_jet.ND_JET_DIMS:
+    if not isinstance(model, ImNet):
+        return False
+    if not ((lig_jet.nd_jets and model.dim in lig_jet.ND_JET_DIMS) or (lig_jet.nd4_jets and model.dim == 4)):
         return False
     if any(not (0 <= a < model.dim and 0 <= b < model.dim) for a, b in req.pairs):
         return False
@@ -140,6 +148,8 @@ def _nd_jet_train_eligible(model, latent_grid, query_pts, req=None):
     if not (lig_jet.nd_jets and lig_jet.nd_jet_backward) or not torch.is_grad_enabled() or query_pts.requires_grad:
         return False
     if isinstance(model, torch.nn.DataParallel) or getattr(model, "in_features", 0) > lig_jet.ND_TRAIN_MAX_CHANNELS:
+        return False
+    if getattr(model, "dim", None) not in lig_jet.ND_JET_DIMS:      # (d = 4, ``nd4_jets``: forward passes only)
         return False
     if req is None or not (req.first or req.pairs):     # (a request for the value alone trains as a value query: ``nd_backward``)
         return False

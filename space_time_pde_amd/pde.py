@@ -752,11 +752,17 @@ class PDELayer(object):
             # switched on as well (``lig_jet.nd_jet_backward``)
             if not (_lig.lig_jet.nd_jets and (not torch.is_grad_enabled() or _lig.lig_jet.nd_jet_backward)):
                 return None
+        elif self.n_in == 4:
+            # (t, x, y, z) problems (opt-in, ``lig_jet.nd4_jets``): forward passes that need no gradient only -- there is no
+            # training backward through these derivatives, so grad mode on keeps the reverse sweeps
+            if not _lig.lig_jet.nd4_jets or torch.is_grad_enabled():
+                return None
         elif self.n_in != 3:
             return None
         if x.requires_grad and torch.is_grad_enabled():
             return None   # the caller wants autograd through the coordinates: only the generic strategy provides it
-        plan = None if nd else self._combo_plan()      # (the combined second-order stream is dim = 3 only: pairs there)
+        # (the combined second-order stream is dim = 3 only: pairs everywhere else)
+        plan = None if (nd or self.n_in == 4) else self._combo_plan()
         if plan is not None:
             return _lig.JetRequest(x, True, [], combo=plan["alpha"])
         first, pairs = False, set()
@@ -771,8 +777,9 @@ class PDELayer(object):
     def _residues_from_jets(self, x, req):
         jets, pairs = req.jets, req.pairs_out
         shape = x.shape[:-1] + (1,)
+        nfirst = 4 if self.n_in == 4 else 3     # first-order streams of the jets tensor (four inputs: 1 .. 4, pairs from 5)
         stream_of = {(): 0}
-        for d in range(3):
+        for d in range(nfirst):
             stream_of[(d,)] = 1 + d
         progs = self.eqns_jet
         if pairs == ["combo"]:
@@ -780,7 +787,7 @@ class PDELayer(object):
             progs = self._combo_plan()["progs"]
         else:
             for k, p in enumerate(pairs):
-                stream_of.setdefault(tuple(p), 4 + k)
+                stream_of.setdefault(tuple(p), 1 + nfirst + k)
         hip = self._residues_hip(x, jets, progs, stream_of, shape)
         if hip is not None:
             return hip
@@ -831,7 +838,9 @@ class PDELayer(object):
         progs = self.eqns_jet
         if not (progs and all(p is not None and p.expr is not None for p in progs.values())):
             return False
-        stream_of = {(): 0, (0,): 1, (1,): 2, (2,): 3}
+        nfirst = 4 if self.n_in == 4 else 3
+        stream_of = {(): 0}
+        stream_of.update({(d,): 1 + d for d in range(nfirst)})
         plan = self._combo_plan() if self.n_in == 3 else None
         if plan is not None:
             stream_of[("L",)] = 4
@@ -839,8 +848,10 @@ class PDELayer(object):
         else:
             pairs = sorted({mi for p in progs.values() for _, mi in p.atoms if len(mi) == 2})
             for k, pr in enumerate(pairs):
-                stream_of[pr] = 4 + k
-        return self._res_program(progs, stream_of, device) is not None
+                stream_of[pr] = 1 + nfirst + k
+        ent = self._res_program(progs, stream_of, device)
+        # (the evaluator addresses coordinates as [P][3]: a program on four inputs that names one is not taken)
+        return ent is not None and not (self.n_in == 4 and ent[2])
 
     def _residues_hip(self, x, jets, progs, stream_of, shape):
         """All residuals of all equations in ONE HIP kernel (and one for the backward) instead of ~100 elementwise
@@ -853,6 +864,8 @@ class PDELayer(object):
         if ent is None:
             return None
         prog_t, nins, uses_x, ks = ent
+        if uses_x and self.n_in > 3:
+            return None     # the evaluator addresses coordinates as [P][3]: the lambdified functions do this layer's algebra
         coefs = []
         if ks:
             vals = self._param_values(x)
